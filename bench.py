@@ -10,11 +10,13 @@ batch of synthetic 320x320 images (BASELINE.json configs[1]: ssdlite320_mobilene
 Timing window = engine.evaluate's (engine.py:86-94): inputs already on the device, synchronize, forward incl.
 post-process, outputs complete on the stream. The K timed steps go through demonet_amd.pipeline.ForwardPipeline: `--inflight`
 (default 3) forwards are kept in flight, each a complete single-chain forward of its own batch on its own stream with its own
-workspace and outputs -- the serving form of the path; `one_at_a_time` in the JSON line repeats the K steps with one forward in
+workspace and outputs -- the serving form of the path; with --full, `one_at_a_time` in the JSON line repeats the K steps with one forward in
 flight (SSD.forward_batch) and `latency` is the per-forward distribution of that mode. N > 1: BASELINE configs[3] -- the global batch 256 is image-sharded, 256 / N per
 rank (--batch overrides the per-GPU size: weak scaling); the fixed-shape
 detections of every step are staged on the device and all-gathered over RCCL one window (16 steps) at a time, the last window
 flushed inside the timed region (the reference gathers once, after the loop: engine.py:105).
+A plain run stops at the headline figure; --full adds the latency passes, the per-kernel roofline, the C3 / C5 configs and the CPU
+baseline to the line. --dump-outputs DIR writes what the last timed step returned (float32 .npy files).
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -336,6 +338,26 @@ def time_config(model_name, batch, image_size, steps, warmup, dev, inflight=3):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: the padded (boxes [B,D,4], scores [B,D], labels [B,D], counts [B]) of one step as <path>/<name>.npy, float32. Past
+    64 MB in all, a fixed seeded sample of the images (the same rows of every array; their indices in images.npy) is written instead."""
+    names = ("boxes", "scores", "labels", "counts")
+    arrs = [t.detach().float().cpu().numpy() for t in outs]
+    n = arrs[0].shape[0]
+    per_img = sum(a[0].nbytes for a in arrs)
+    if n * per_img > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, (DUMP_LIMIT_BYTES - 4096) // (per_img + 4), replace=False))     # (4 KB: the .npy headers)
+        arrs = [a[keep] for a in arrs]
+        names += ("images",)
+        arrs.append(keep.astype(np.float32))
+    os.makedirs(path, exist_ok=True)
+    for nm, a in zip(names, arrs):
+        np.save(os.path.join(path, nm + ".npy"), a)
+
+
 def _on(stream):
     import contextlib
     return contextlib.nullcontext() if stream is None else torch.cuda.stream(stream)
@@ -365,8 +387,15 @@ def main(argv=None):
                     "images up). The PMC passes of tools/round_profile.sh use --eager --chains 1: the kernels at the launch size of the timed region")
     ap.add_argument("--no-latency", action="store_true", help="skip the per-step latency percentiles / D2H-inclusive step time (extra passes after the timed region)")
     ap.add_argument("--per-op", default="", help="write a per-op table (time, GB/s, TFLOP/s) to this file")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C3 / C5 legs (BASELINE configs[2] and [4]) that the default single-GPU run times behind the C2 sections")
+    ap.add_argument("--no-configs", action="store_true", help="skip the C3 / C5 legs (BASELINE configs[2] and [4]) that the --full single-GPU run times behind the C2 sections")
+    ap.add_argument("--full", action="store_true", help="after the headline figure, also measure the rest: latency passes and the one-at-a-time mode, "
+                    "the per-kernel roofline pass, the C3 / C5 configs and the CPU baseline (each still switched off by its --no-* option). "
+                    "Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned "
+                    "(padded boxes, scores, labels, counts of rank 0's batch) as DIR/<name>.npy in float32")
     args = ap.parse_args(argv)
+    if args.per_op and not args.full:
+        ap.error("--per-op needs --full (the per-op table comes from the roofline pass)")
     stub = args.stub_cpu
 
     if args.gpus < 1:
@@ -468,6 +497,7 @@ def main(argv=None):
             batches = [images_u8] + [to_u8(x) for x in batches[1:]]
     nstep = [0]
     last_ticket = [-1]
+    last_out = [None]          # one forward at a time: the padded tensors the last step returned (--dump-outputs)
 
     def step():
         if pipe is not None:
@@ -481,13 +511,13 @@ def main(argv=None):
                     last_ticket[0] = gatherer.submit(src=pipe.packed(t), join=pipe.join)
             return t
         if distributed:
-            boxes, scores, labels, counts = model.forward_batch(images, persistent_input=True, packed=gatherer.next_buffer())
+            last_out[0] = model.forward_batch(images, persistent_input=True, packed=gatherer.next_buffer())
             gatherer.submit()
         elif images_u8 is not None:
-            boxes, scores, labels, counts = model.forward_uint8(images_u8)
+            last_out[0] = model.forward_uint8(images_u8)
         else:
-            boxes, scores, labels, counts = model.forward_batch(images, persistent_input=True)
-        return counts
+            last_out[0] = model.forward_batch(images, persistent_input=True)
+        return last_out[0][3]
 
     for _ in range(max(args.warmup, 2 * R)):
         step()
@@ -515,6 +545,8 @@ def main(argv=None):
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt          # whole-job aggregate: every rank processed B images per step
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pipe.result(counts) if pipe is not None else last_out[0])
     if stub:
         # what the last step's gather holds on every rank: the global batch in image order, every rank's shard where shard_range put it
         total_steps = max(args.warmup, 2 * R) + args.steps
@@ -563,7 +595,7 @@ def main(argv=None):
     if args.weights != "calibrated":
         result["config"]["workload"] += f", {args.weights} class-head weights"
 
-    if rank == 0 and not args.no_latency and not distributed:
+    if rank == 0 and args.full and not args.no_latency and not distributed:
         # per-step distribution (one forward in flight at a time) and the window of engine.py:86-94 with the
         # detections copied to the host inside it. Extra passes after the timed region; `value` is unaffected.
         lat = []
@@ -614,7 +646,7 @@ def main(argv=None):
                              "ms_per_step_with_d2h": round(d2h_ms, 4),
                              "d2h_bytes": int(sum(t.numel() * t.element_size() for t in host))}
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # per-kernel device time: HIP events around every launch on the forward stream (eager pass, same inputs)
         from demonet_amd import _lib
         L = _lib.lib()
@@ -808,7 +840,7 @@ def main(argv=None):
                                  "TFLOP/s": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 2), "launches": v["launches"],
                                  "share": round(v["ms"] / total_ms, 3)}
                              for k, v in sorted(agg.items(), key=lambda kv: -kv[1]["ms"])}
-    if rank == 0 and world == 1 and not distributed and not args.no_configs and args.model == DEFAULT_MODEL and B == DEFAULT_BATCH and args.weights == "calibrated":
+    if rank == 0 and world == 1 and not distributed and args.full and not args.no_configs and args.model == DEFAULT_MODEL and B == DEFAULT_BATCH and args.weights == "calibrated":
         # the other single-GPU BASELINE configs, same loop, same process (bounded: K steps each): C3 = configs[2], C5 = configs[4]
         model = None
         torch.cuda.empty_cache()
@@ -816,7 +848,7 @@ def main(argv=None):
                                     "forwards_in_flight": R, "workload": result["config"]["workload"]},
                              "C3": time_config("ssd_lite_mobilenet_v2", 128, 300, args.steps, args.warmup, dev),
                              "C5": time_config("ssd512_vgg16", 32, 0, args.steps, args.warmup, dev)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.model, g, 1002)
     if distributed:
         dist.destroy_process_group()

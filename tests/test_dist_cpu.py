@@ -151,6 +151,50 @@ def test_bench_gpus_n_without_a_launcher_starts_n_ranks():
     assert d["n_gpus"] == 2 and d["rccl_ranks_seen"] == 2 and d["stub_check"] and d["per_rank_batch"] == 128 and d["scaling"] == "strong"
 
 
+def _load_bench():
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_dump", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: after the K timed steps, rank 0 writes what its last step returned (padded boxes, scores, labels, counts) as
+    float32 .npy files; with the stub forward that is the payload of step warm-up + K - 1 (warm-up = max(W, 2 x forwards in flight))."""
+    import json
+    import numpy as np
+    bench = _load_bench()
+    p = _run_bench(["--gpus", "2", "--steps", "7", "--warmup", "3", "--stub-cpu", "--dump-outputs", str(tmp_path)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 7 and d["ms_per_step"] > 0 and d["stub_check"]
+    B, D = d["per_rank_batch"], 300
+    want = bench._StubPipe.payload(B, D, 0, 6 + 7 - 1)
+    got = {n: np.load(os.path.join(tmp_path, n + ".npy")) for n in ("boxes", "scores", "labels", "counts")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["boxes"], want[:, :D, :4].numpy()) and np.array_equal(got["scores"], want[:, :D, 4].numpy())
+    assert np.array_equal(got["labels"], want[:, :D, 5].numpy()) and np.array_equal(got["counts"], want[:, D, 0].numpy())
+
+
+def test_bench_dump_outputs_samples_past_64_mb(tmp_path):
+    """More than 64 MB of outputs: a fixed seeded sample of the images, the same rows of every array, their indices in images.npy."""
+    import numpy as np
+    bench = _load_bench()
+    n, D = 12000, 300                                       # 12000 x 300 x 6 x 4 B = 86 MB
+    outs = (torch.rand(n, D, 4), torch.rand(n, D), torch.randint(0, 91, (n, D)), torch.randint(0, D, (n,), dtype=torch.int32))
+    for sub in ("a", "b"):
+        bench.dump_outputs(os.path.join(tmp_path, sub), outs)
+    files = sorted(os.listdir(os.path.join(tmp_path, "a")))
+    assert files == ["boxes.npy", "counts.npy", "images.npy", "labels.npy", "scores.npy"]
+    assert sum(os.path.getsize(os.path.join(tmp_path, "a", f)) for f in files) <= 64 << 20
+    idx = np.load(os.path.join(tmp_path, "a", "images.npy")).astype(np.int64)
+    assert np.array_equal(idx, np.load(os.path.join(tmp_path, "b", "images.npy")).astype(np.int64)) and len(set(idx.tolist())) == len(idx)
+    assert np.array_equal(np.load(os.path.join(tmp_path, "a", "boxes.npy")), outs[0].numpy()[idx])
+    assert np.array_equal(np.load(os.path.join(tmp_path, "a", "counts.npy")), outs[3].numpy()[idx].astype(np.float32))
+
+
 def test_bench_refuses_a_world_size_that_contradicts_gpus():
     p = _run_bench(["--gpus", "8", "--steps", "2", "--warmup", "1", "--stub-cpu"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0 and "WORLD_SIZE=1" in p.stderr

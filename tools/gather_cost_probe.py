@@ -86,4 +86,4 @@ if mode in ("plain_gloo", "plain_destroy", "plain_initonly", "plain_barrier"):
     mode = "plain"
 if mode != "plain":
     os.environ["DN_BENCH_FORCE_DIST"] = "1"
-r = bench.main(["--batch", os.environ.get("GP_BATCH", "32"), "--steps", "800", "--no-cpu-baseline", "--no-roofline"] + os.environ.get("GP_EXTRA", "--no-latency").split())
+r = bench.main(["--batch", os.environ.get("GP_BATCH", "32"), "--steps", "800", "--full", "--no-cpu-baseline", "--no-roofline"] + os.environ.get("GP_EXTRA", "--no-latency").split())

@@ -24,6 +24,6 @@ python3 tools/pmc_mfma.py /tmp/rp_$TAG/sq $OUT/mfma_util.json $OUT/kernel_stats_
 rm -rf /tmp/rp_$TAG
 # the summaries of this build become the committed ones the bench line quotes
 for f in kernel_stats.csv kernel_stats_one_forward.csv hbm_traffic.json mfma_util.json; do cp $OUT/$f profiles/${TAG}_$f; done
-python3 bench.py --per-op $OUT/per_op.txt "$@" > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full --per-op $OUT/per_op.txt "$@" > $OUT/bench.json 2> $OUT/bench.err
 tail -c 1500 $OUT/bench.json; echo
 ls $OUT
