@@ -119,6 +119,11 @@ __device__ __forceinline__ void hf_fma8v(float (&acc)[8], const u32x4& x, const 
 // through the same two xor-shuffles in the same order (pp_softmax_row's arithmetic, bit for bit), then score = e * (1 / sum) straight to memory -- a store
 // instruction writes four classes x 16 consecutive anchors (64 contiguous bytes each). The per-class counts of passing scores, ballots in hf_scores (a
 // class belonged to one wave there), are LDS atomics here like the histogram bins: passing scores are a few per cent.
+// A row lives in registers: HF_SM_BATCHES batches of 8 elements per lane, four lanes per row -- classes k < 32 * HF_SM_BATCHES. Larger K must not
+// reach this epilogue (head_fused_post_supported refuses it; those levels keep the logit-writing launch and softmax_decode_kernel).
+constexpr int HF_SM_BATCHES = 3;
+constexpr int HF_SM_MAX_K = 4 * 8 * HF_SM_BATCHES;
+static_assert(HF_SM_MAX_K == 96, "hf_softmax_scores covers 96 classes: change head_fused_post_supported's bound with it");
 __device__ __forceinline__ void hf_softmax_scores(const HeadPost& P, const float* __restrict__ lg, const unsigned* __restrict__ rowoff, const unsigned* __restrict__ ranc,
                                                   const unsigned char* __restrict__ rpart, unsigned* __restrict__ lhist, const int nrows, const int img_first,
                                                   const int te, const int K, const int ccb) {
@@ -131,9 +136,9 @@ __device__ __forceinline__ void hf_softmax_scores(const HeadPost& P, const float
         const bool valid = row < nrows;
         const float* rp = lg + (valid ? rowoff[row] : 0u);
         float mx = -INFINITY, sm = 0.f;
-        float v[24];                                        // element 8 b + u <-> class k = sub + 32 b + 4 u (pp_softmax_row's batches)
+        float v[8 * HF_SM_BATCHES];                         // element 8 b + u <-> class k = sub + 32 b + 4 u (pp_softmax_row's batches)
 #pragma unroll
-        for (int b = 0; b < 3; ++b) {
+        for (int b = 0; b < HF_SM_BATCHES; ++b) {
 #pragma unroll
             for (int u = 0; u < 8; ++u) v[8 * b + u] = rp[min(sub + 32 * b + 4 * u, K - 1)];
 #pragma unroll
@@ -142,7 +147,7 @@ __device__ __forceinline__ void hf_softmax_scores(const HeadPost& P, const float
         mx = fmaxf(mx, __shfl_xor(mx, 1));
         mx = fmaxf(mx, __shfl_xor(mx, 2));
 #pragma unroll
-        for (int b = 0; b < 3; ++b) {
+        for (int b = 0; b < HF_SM_BATCHES; ++b) {
 #pragma unroll
             for (int u = 0; u < 8; ++u) v[8 * b + u] = pp_exp_nonpos(v[8 * b + u] - mx);
 #pragma unroll
@@ -160,7 +165,7 @@ __device__ __forceinline__ void hf_softmax_scores(const HeadPost& P, const float
         const unsigned hb = q * 256u;
         const unsigned ob4 = (((unsigned)(img_first + (int)q) * (unsigned)Km1) * (unsigned)P.A + ranc[rw]) * 4u + (unsigned)(sub - 1) * step4;     // class sub - 1 (sub = 0: the background, skipped)
 #pragma unroll
-        for (int b = 0; b < 3; ++b)
+        for (int b = 0; b < HF_SM_BATCHES; ++b)
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int k = sub + 32 * b + 4 * u;
@@ -596,6 +601,7 @@ extern "C" __attribute__((visibility("default"))) int dn_debug_head_softmax_laun
 
 bool head_fused_post_supported(const HeadFuseLevel* lv, int count, const HeadPost& post) {
     if (!post.scoresT || !post.boxes || !post.hrows || !post.anchors || post.K < 2 || post.A < 1 || post.nb < 1 || post.nb > 256) return false;
+    if (post.K > HF_SM_MAX_K) return false;      // hf_softmax_scores holds 96 classes of a row (the LDS bound below stops 6-anchor levels at K = 92 already)
     int rows = 0, nsm = 0;
     for (int i = 0; i < count; ++i) {
         const HeadFuseLevel& l = lv[i];

@@ -297,6 +297,10 @@ extern "C" int dn_create(const dn_model_desc* desc, const void* weights, size_t 
     DN_REQUIRE(desc->n_tensors > 0 && desc->n_ops > 0 && desc->tensors && desc->ops, "dn_create: empty graph");
     DN_REQUIRE(desc->n_levels >= 1 && desc->n_levels <= 8, "dn_create: n_levels=%d outside [1,8]", desc->n_levels);
     DN_REQUIRE(desc->num_classes >= 2, "dn_create: num_classes must include background (>= 2)");
+    if (desc->num_classes > DN_MAX_CLASSES) {
+        dn_set_error("dn_create: num_classes=%d above the limit of %d (DN_MAX_CLASSES, background included)", desc->num_classes, DN_MAX_CLASSES);
+        return DN_E_UNSUPPORTED;
+    }
     DN_REQUIRE(desc->anchors && desc->num_anchors > 0, "dn_create: anchors missing");
     DN_REQUIRE(desc->score_thresh >= 0.f, "dn_create: score_thresh must be >= 0");
     dn_plan* p = new dn_plan();
@@ -1455,6 +1459,10 @@ extern "C" int dn_postprocess(const float* logits, const float* reg, const float
                               size_t ws_bytes, void* stream) {
     DN_REQUIRE(logits && reg && anchors && boxes && scores && labels && counts && ws, "dn_postprocess: null argument");
     DN_REQUIRE(score_thresh >= 0.f, "dn_postprocess: score_thresh must be >= 0");
+    if (K > DN_MAX_CLASSES) {
+        dn_set_error("dn_postprocess: num_classes=%d above the limit of %d (DN_MAX_CLASSES, background included)", K, DN_MAX_CLASSES);
+        return DN_E_UNSUPPORTED;
+    }
     PostArgs a;
     a.logits = logits; a.reg = reg; a.anchors = anchors; a.n = n; a.A = A; a.K = K;
     a.img_h = image_h; a.img_w = image_w; a.scale_xy = scale_xy;

@@ -242,6 +242,106 @@ __global__ __launch_bounds__(256) void softmax_decode_kernel(const float* __rest
     PP_STAMP(12);
 }
 
+// P1 for K - 1 > 256 foreground classes (LVIS-size vocabularies), where a [64][K] tile no longer fits the LDS. Same 64-anchor tiles, same
+// histogram rows (the per-class count bins are off at this K: nb + K - 1 > HBINS), same helpers of post_math.h; the summation order differs from
+// softmax_decode_kernel's (no path at this K has to match it bit for bit).
+//   pass 1: one wave per row at a time, the row read straight from memory (64 lanes x 4 B contiguous per load, 16 loads in flight per lane),
+//           a running (max, sum) per lane, then combined over the wave: max -> rowmax, 1 / sum -> rowrcp. No LDS but the two 64-entry tables.
+//   pass 2: the tile again in chunks of 64 anchors x WIDE_KC classes through LDS (row stride WIDE_KC + 1: the transposed reads are free of bank
+//           conflicts); the next chunk's loads are in flight in registers while this chunk's scores go out, class-major, one class's 64 anchors
+//           (256 contiguous bytes) per wave store.
+constexpr int WIDE_KC = 128;                 // classes per chunk
+constexpr int WIDE_KCP = WIDE_KC + 1;        // LDS row stride (floats)
+constexpr int WIDE_PF = 64 * WIDE_KC / 256;  // chunk elements per thread (32: the prefetch registers)
+constexpr size_t WIDE_LDS = (size_t)64 * WIDE_KCP * 4 + 64 * 4 * 2 + HBINS * 4;
+static_assert(WIDE_LDS <= 64 * 1024, "the wide softmax must leave room for two workgroups per CU");
+
+template <bool PERM>
+__global__ __launch_bounds__(256) void softmax_decode_wide_kernel(const float* __restrict__ logits, const float* __restrict__ reg,
+                                                                 const float* __restrict__ anchors, float* __restrict__ scoresT,
+                                                                 float4* __restrict__ boxes, int A, int K, float img_w, float img_h,
+                                                                 float score_thr, unsigned* __restrict__ phist, int hb0, int nb,
+                                                                 int nimg, int tiles, int xq, PostLevels lv) {
+#pragma clang fp contract(off)
+    __shared__ float tile[64 * WIDE_KCP];
+    __shared__ float rowmax[64], rowrcp[64];
+    __shared__ unsigned lhist[HBINS];
+    __shared__ int pidx[64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int n, atile;
+    if (!xcd_image_of(blockIdx.x, tiles, xq, nimg, n, atile)) return;
+    const int a0 = atile * 64, na = min(64, A - a0), Km1 = K - 1;
+    lhist[tid] = 0u;                               // (HBINS == 256 == threads)
+    if (PERM && tid < 64) pidx[tid] = post_perm(lv, min(a0 + tid, A - 1));
+    const float* const src = logits + ((size_t)n * A + a0) * K;
+
+    // pass 1: row maximum and 1 / sum over all K classes (background included)
+    for (int r = wave; r < na; r += 4) {
+        const float* row = src + (size_t)r * K;
+        float m = -INFINITY, s = 0.f;
+        for (int k0 = lane; k0 < K; k0 += 64 * 16) {
+            float v[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) v[u] = row[min(k0 + 64 * u, K - 1)];      // (a clamped index re-reads an element of this row)
+            float bm = m;
+#pragma unroll
+            for (int u = 0; u < 16; ++u) bm = fmaxf(bm, v[u]);
+            s *= pp_exp_nonpos(m - bm);                                            // (m = -inf at the start: exp -> 0, s stays 0)
+#pragma unroll
+            for (int u = 0; u < 16; ++u)
+                if (k0 + 64 * u < K) s += pp_exp_nonpos(v[u] - bm);
+            m = bm;
+        }
+        float M = m;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) M = fmaxf(M, __shfl_xor(M, d));
+        s *= pp_exp_nonpos(m - M);
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+        if (lane == 0) { rowmax[r] = M; rowrcp[r] = pp_row_rcp(s); }
+    }
+
+    // pass 2: chunks of classes [k0, k0 + kc), k0 = 1, 1 + WIDE_KC, ... (the background's scores are not stored)
+    float pf[WIDE_PF];
+    auto load_chunk = [&](int k0) {
+        const int kc = min(WIDE_KC, K - k0);
+#pragma unroll
+        for (int u = 0; u < WIDE_PF; ++u) {
+            const int idx = tid + 256 * u, r = idx / WIDE_KC, kk = idx - r * WIDE_KC;     // (power of two: shifts)
+            pf[u] = (r < na && kk < kc) ? src[(size_t)r * K + k0 + kk] : 0.f;
+        }
+    };
+    load_chunk(1);
+    for (int k0 = 1; k0 < K; k0 += WIDE_KC) {
+        const int kc = min(WIDE_KC, K - k0);
+        __syncthreads();                           // the previous chunk's reads of `tile` are done (first pass: rowmax / rowrcp / pidx / lhist are ready)
+#pragma unroll
+        for (int u = 0; u < WIDE_PF; ++u) {
+            const int idx = tid + 256 * u, r = idx / WIDE_KC, kk = idx - r * WIDE_KC;
+            tile[r * WIDE_KCP + kk] = pf[u];
+        }
+        __syncthreads();
+        if (k0 + WIDE_KC < K) load_chunk(k0 + WIDE_KC);      // in flight while this chunk is written out
+        for (int idx = tid; idx < kc * 64; idx += 256) {
+            const int kk = idx >> 6, a = idx & 63;
+            if (a < na) {
+                const float sc = pp_score(pp_exp_nonpos(tile[a * WIDE_KCP + kk] - rowmax[a]), rowrcp[a]);
+                scoresT[((size_t)n * Km1 + (k0 + kk - 1)) * A + (PERM ? pidx[a] : a0 + a)] = sc;
+                if (sc > score_thr) atomicAdd(&lhist[pp_hist_bin(sc, hb0, nb)], 1u);
+            }
+        }
+    }
+    if (tid < na) {
+        const int a = a0 + tid;
+        const float4 rg = reinterpret_cast<const float4*>(reg)[(size_t)n * A + a];
+        const float4 an = reinterpret_cast<const float4*>(anchors)[a];
+        boxes[(size_t)n * A + a] = pp_decode_box(rg, an, img_w, img_h);
+    }
+    __syncthreads();
+    // the tile's histogram row (tau_kernel adds the rows of the image)
+    phist[(((size_t)n * tiles + atile) << 8) + tid] = tid < nb ? lhist[tid] : 0u;
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // block-level helpers shared by P2 and P3
 // ------------------------------------------------------------------------------------------------------------
@@ -601,10 +701,14 @@ struct MergeArgs {
     const unsigned* tauKey; int* needFull; int D;
 };
 constexpr int MERGE_LCAP = 3072;
-// LDS of the merge, carved from one buffer (the stand-alone launch owns a static one; the fused fallback launch lends the selection's dynamic LDS)
-constexpr int MERGE_LDS = 2 * 512 * 8 + MERGE_LCAP * (8 + 4 + 2) + 256 * 4 + 256 + 256 * 4 + 1040;
+// LDS of the merge, carved from one buffer (the stand-alone launch owns a static one; the fused fallback launch lends the selection's dynamic LDS).
+// CCAP: class capacity of the per-class counts / prefix sums -- 256 up to 257 classes, DN_MAX_CLASSES beyond (16 KB of the buffer).
+constexpr int merge_lds_bytes(int ccap) { return 2 * 512 * 8 + MERGE_LCAP * (8 + 4 + 2) + 256 * 4 + 256 + ccap * 4 + ccap * 4 + 16; }
+constexpr int MERGE_LDS = merge_lds_bytes(256);
+constexpr int MERGE_CCAP_WIDE = DN_MAX_CLASSES;          // (>= Km1 + 1 for every K the library accepts)
+constexpr int MERGE_LDS_WIDE = merge_lds_bytes(MERGE_CCAP_WIDE);
 
-template <int MT>
+template <int MT, int CCAP = 256>
 __device__ __forceinline__ void merge_body(char* __restrict__ mlds, const float* __restrict__ keptScore, const int* __restrict__ keptAnchor,
                                            const int* __restrict__ keptCount, const float4* __restrict__ boxes, int A, int Km1, int topk,
                                            const MergeArgs& g, int mode, int n);
@@ -762,8 +866,8 @@ __global__ __launch_bounds__(FT) void select_nms_fast_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------------------------
 // P3: per image
 // ------------------------------------------------------------------------------------------------------------
-template <int MT>       // threads per workgroup: 1024 sorts fastest, 256 is scheduled at once beside the other chain's kernels (a 1024-thread
-                        // workgroup waits for 16 free wave slots on ONE compute unit)
+template <int MT, int CCAP>       // threads per workgroup: 1024 sorts fastest, 256 is scheduled at once beside the other chain's kernels (a 1024-thread
+                                  // workgroup waits for 16 free wave slots on ONE compute unit); CCAP: class capacity (>= Km1 + 1)
 __device__ __forceinline__ void merge_body(char* __restrict__ mlds, const float* __restrict__ keptScore, const int* __restrict__ keptAnchor,
                                            const int* __restrict__ keptCount, const float4* __restrict__ boxes, int A, int Km1, int topk,
                                            const MergeArgs& g, int mode, int n) {
@@ -781,8 +885,8 @@ __device__ __forceinline__ void merge_body(char* __restrict__ mlds, const float*
     unsigned short* llab = reinterpret_cast<unsigned short*>(lanc + MERGE_LCAP);     // [MERGE_LCAP]
     unsigned* hist = reinterpret_cast<unsigned*>(llab + MERGE_LCAP);                 // [256]
     unsigned* sh = hist + 256;                                                       // [40] (64 reserved)
-    int* ccount = reinterpret_cast<int*>(sh + 64);                                   // [256]
-    int* cpre = ccount + 256;                                                        // [257]
+    int* ccount = reinterpret_cast<int*>(sh + 64);                                   // [CCAP]
+    int* cpre = ccount + CCAP;                                                       // [CCAP + 1]
     const int tid = threadIdx.x;
     const int F = Km1 * topk;
     const float* ks = keptScore + (size_t)n * F;
@@ -807,7 +911,7 @@ __device__ __forceinline__ void merge_body(char* __restrict__ mlds, const float*
     // survivors live in per-class slots [c][0..ccount[c]); walk them through the class prefix sums (e -> class by binary
     // search) instead of scanning all Km1*topk slots: `total` is a few thousand, the slot array 27k.
     if (tid < 64) {
-        // exclusive scan of ccount over classes, one wave (Km1 <= 256)
+        // exclusive scan of ccount over classes, one wave (64 classes per step)
         int run = 0;
         for (int c0 = 0; c0 < Km1; c0 += 64) {
             const int c = c0 + tid;
@@ -947,7 +1051,20 @@ __global__ __launch_bounds__(MT) void merge_kernel(const float* __restrict__ kep
     if (!xcd_image_of(blockIdx.x, 1, xq, nimg, n, unused)) return;
     if (mode == 0 && g.needFull[n]) return;
     if (mode == 1 && !g.needFull[n]) return;
-    merge_body<MT>(mlds, keptScore, keptAnchor, keptCount, boxes, A, Km1, topk, g, mode, n);
+    merge_body<MT, 256>(mlds, keptScore, keptAnchor, keptCount, boxes, A, Km1, topk, g, mode, n);
+}
+
+// more than 256 foreground classes: per-class arrays for DN_MAX_CLASSES (dynamic LDS, MERGE_LDS_WIDE bytes)
+template <int MT>
+__global__ __launch_bounds__(MT) void merge_wide_kernel(const float* __restrict__ keptScore, const int* __restrict__ keptAnchor,
+                                                         const int* __restrict__ keptCount, const float4* __restrict__ boxes, int A, int Km1, int topk,
+                                                         MergeArgs g, int mode, int nimg, int xq) {
+    extern __shared__ __attribute__((aligned(16))) char mlds_dyn[];
+    int n, unused;
+    if (!xcd_image_of(blockIdx.x, 1, xq, nimg, n, unused)) return;
+    if (mode == 0 && g.needFull[n]) return;
+    if (mode == 1 && !g.needFull[n]) return;
+    merge_body<MT, MERGE_CCAP_WIDE>(mlds_dyn, keptScore, keptAnchor, keptCount, boxes, A, Km1, topk, g, mode, n);
 }
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1054,7 +1171,13 @@ int launch_postprocess(const PostArgs& a0, hipStream_t s, hipEvent_t* ev) {
     DN_REQUIRE(a.n > 0 && a.A > 0 && a.K >= 2, "postprocess: bad sizes n=%d A=%d K=%d", a.n, a.A, a.K);
     DN_REQUIRE(a.topk >= 1 && a.topk <= 512, "postprocess: topk_candidates=%d outside [1,512]", a.topk);
     DN_REQUIRE(a.dets >= 1 && a.dets <= 512, "postprocess: detections_per_img=%d outside [1,512]", a.dets);
-    DN_REQUIRE(a.K - 1 <= 256, "postprocess: more than 256 foreground classes");
+    if (a.K > DN_MAX_CLASSES) {
+        dn_set_error("postprocess: num_classes=%d above the limit of %d (DN_MAX_CLASSES, background included)", a.K, DN_MAX_CLASSES);
+        return DN_E_UNSUPPORTED;
+    }
+    // more than 256 foreground classes: softmax_decode_wide_kernel, the wide merge instantiations (per-class arrays for DN_MAX_CLASSES)
+    const bool wide = a.K - 1 > 256;
+    DN_REQUIRE(!wide || !a.scores_ready, "postprocess: scores from the head launch with %d classes (the fused epilogue stops at 96)", a.K);
     const size_t need = postprocess_ws_bytes(a.n, a.A, a.K, a.topk, a.dets);
     if (a.ws_bytes < need) {
         dn_set_error("postprocess: workspace %zu B < required %zu B", a.ws_bytes, need);
@@ -1108,7 +1231,18 @@ int launch_postprocess(const PostArgs& a0, hipStream_t s, hipEvent_t* ev) {
         const long long* const stp = nullptr;       // (dev builds stamp the selection kernels; this launch is not stamped)
         const int t1 = a.scores_ready ? small_tiles : tiles, abase = a.scores_ready ? a.small_first : 0;
         const int rstride = a.scores_ready ? hrows.rows_per_image : tiles, rbase = a.scores_ready ? hrows.extra_base : 0;
-        if (t1 > 0) {
+        if (t1 > 0 && wide) {
+            if (!(a.lv.n == 1 && a.lv.aloc[0] == 1))
+                hipLaunchKernelGGL(softmax_decode_wide_kernel<true>, dim3(t1 * slots), dim3(256), 0, s, a.logits, a.reg, a.anchors, scoresT, boxes,
+                                   a.A, a.K, a.img_w, a.img_h, a.score_thresh, phist, hb0, nb, a.n, t1, a.xq, a.lv);
+            else
+                hipLaunchKernelGGL(softmax_decode_wide_kernel<false>, dim3(t1 * slots), dim3(256), 0, s, a.logits, a.reg, a.anchors, scoresT, boxes,
+                                   a.A, a.K, a.img_w, a.img_h, a.score_thresh, phist, hb0, nb, a.n, t1, a.xq, a.lv);
+        } else if (t1 > 0) {
+            if (lds1 > 64 * 1024) {       // (K above ~250: the [64][K] tile passes 64 KB)
+                DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(softmax_decode_kernel<true>), 160 * 1024 - 1024));      // (minus the static pidx[] / ticket flag)
+                DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(softmax_decode_kernel<false>), 160 * 1024 - 1024));
+            }
             if (!(a.lv.n == 1 && a.lv.aloc[0] == 1))
                 hipLaunchKernelGGL(softmax_decode_kernel<true>, dim3(t1 * slots), dim3(256), lds1, s, a.logits, a.reg, a.anchors,
                                    scoresT, boxes, a.A, a.K, a.img_w, a.img_h, a.score_thresh, phist, hb0, nb, const_cast<long long*>(stp),
@@ -1130,14 +1264,20 @@ int launch_postprocess(const PostArgs& a0, hipStream_t s, hipEvent_t* ev) {
         else if (nw <= 5) rc = launch_p2_fast<5>(a, scoresT, boxes, tauKey, needFull, keptScore, keptAnchor, keptCount, ord, s);
         else rc = launch_p2_fast<8>(a, scoresT, boxes, tauKey, needFull, keptScore, keptAnchor, keptCount, ord, s);
         if (ev) (void)hipEventRecord(ev[2], s);
-        hipLaunchKernelGGL(merge_kernel<1024>, dim3(slots), dim3(1024), 0, s, keptScore, keptAnchor, keptCount, boxes, a.A, (int)Km1, a.topk, mg, 0, a.n, a.xq);
+        if (wide) {
+            DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(merge_wide_kernel<1024>), MERGE_LDS_WIDE));
+            hipLaunchKernelGGL(merge_wide_kernel<1024>, dim3(slots), dim3(1024), MERGE_LDS_WIDE, s, keptScore, keptAnchor, keptCount, boxes, a.A, (int)Km1, a.topk, mg, 0, a.n, a.xq);
+        } else
+            hipLaunchKernelGGL(merge_kernel<1024>, dim3(slots), dim3(1024), 0, s, keptScore, keptAnchor, keptCount, boxes, a.A, (int)Km1, a.topk, mg, 0, a.n, a.xq);
     }
     else if (ev) (void)hipEventRecord(ev[2], s);
     if (ev) (void)hipEventRecord(ev[3], s);
     const int* flag = fast ? needFull : nullptr;
     // behind the cut-off pass: ONE launch redoes the flagged images (usually none) with the full kernel and merges each in the workgroup that
     // finishes its last class (DN_PP_FUSE_FALLBACK, default 1; 0: a second merge launch as in rounds 1 - 3)
-    const bool fuse_fb = fast && dn_knob("DN_PP_FUSE_FALLBACK", 1) != 0;
+    // (more than 256 foreground classes: never fused -- the selection kernel's merge has per-class arrays for 256 classes; merge_wide_kernel<256>
+    // is the second launch)
+    const bool fuse_fb = fast && !wide && dn_knob("DN_PP_FUSE_FALLBACK", 1) != 0;
     int* fb = fuse_fb ? fbcnt : nullptr;
     if (nw <= 1) rc = launch_p2<1>(a, scoresT, boxes, keptScore, keptAnchor, keptCount, flag, mg, fb, s);
     else if (nw <= 2) rc = launch_p2<2>(a, scoresT, boxes, keptScore, keptAnchor, keptCount, flag, mg, fb, s);
@@ -1147,7 +1287,14 @@ int launch_postprocess(const PostArgs& a0, hipStream_t s, hipEvent_t* ev) {
     if (rc != DN_OK) return rc;
     if (!fuse_fb) {
         // the merge after the full pass: with the fast path on it only works for flagged images (usually none): 256 threads, scheduled at once
-        if (fast)
+        if (wide) {
+            DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(merge_wide_kernel<256>), MERGE_LDS_WIDE));
+            DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(merge_wide_kernel<1024>), MERGE_LDS_WIDE));
+            if (fast)
+                hipLaunchKernelGGL(merge_wide_kernel<256>, dim3(slots), dim3(256), MERGE_LDS_WIDE, s, keptScore, keptAnchor, keptCount, boxes, a.A, (int)Km1, a.topk, mg, 1, a.n, a.xq);
+            else
+                hipLaunchKernelGGL(merge_wide_kernel<1024>, dim3(slots), dim3(1024), MERGE_LDS_WIDE, s, keptScore, keptAnchor, keptCount, boxes, a.A, (int)Km1, a.topk, mg, 2, a.n, a.xq);
+        } else if (fast)
             hipLaunchKernelGGL(merge_kernel<256>, dim3(slots), dim3(256), 0, s, keptScore, keptAnchor, keptCount, boxes, a.A, (int)Km1, a.topk, mg, 1, a.n, a.xq);
         else
             hipLaunchKernelGGL(merge_kernel<1024>, dim3(slots), dim3(1024), 0, s, keptScore, keptAnchor, keptCount, boxes, a.A, (int)Km1, a.topk, mg, fast ? 1 : 2, a.n, a.xq);

@@ -20,6 +20,9 @@ extern "C" {
 #endif
 
 #define DN_ABI_VERSION 1
+/* Largest num_classes (background included) dn_create, dn_forward* and dn_postprocess accept: LVIS v1 (1 204), OpenImages (601) and
+ * Objects365 (366) fit. Above it they return DN_E_UNSUPPORTED. */
+#define DN_MAX_CLASSES 2048
 #define DN_API __attribute__((visibility("default")))
 
 enum { DN_OK = 0, DN_E_INVALID = -1, DN_E_HIP = -2, DN_E_WORKSPACE = -3, DN_E_UNSUPPORTED = -4 };
@@ -67,7 +70,7 @@ typedef struct dn_model_desc {
     int32_t input_tensor;
     int32_t image_h, image_w;           /* fixed network input size (generalized_ssd.py:190-191) */
     float mean[3], std[3];              /* transform.py:129-138 */
-    int32_t num_classes;                /* including background class 0 */
+    int32_t num_classes;                /* including background class 0; 2 .. DN_MAX_CLASSES (dn_create returns DN_E_UNSUPPORTED above) */
     int32_t n_levels;
     int32_t level_tensor[8];            /* feature-map tensor id per pyramid level */
     int32_t anchors_per_loc[8];
@@ -116,7 +119,8 @@ DN_API int dn_tensor_ptr(const dn_plan* plan, void* workspace_dev, int n, int te
 
 /* Post-process only, replacing SSD.postprocess_detections (generalized_ssd.py:351-397) + transform.postprocess:
  * softmax -> decode (BoxCoder weights 10,10,5,5) -> clip -> per-class score>thr & top-k -> hard NMS (IoU > thr)
- * -> global top-D by score.  kept_anchor_dev (optional, may be NULL): [n][D] int32 anchor index per detection. */
+ * -> global top-D by score.  kept_anchor_dev (optional, may be NULL): [n][D] int32 anchor index per detection.
+ * num_classes (background included) 2 .. DN_MAX_CLASSES: DN_E_UNSUPPORTED above; topk_candidates and detections_per_img 1 .. 512. */
 DN_API size_t dn_postprocess_workspace_bytes(int n, int num_anchors, int num_classes, int topk_candidates, int detections_per_img);
 DN_API int dn_postprocess(const float* cls_logits_dev, const float* bbox_regression_dev, const float* anchors_dev,
                    int n, int num_anchors, int num_classes,
