@@ -59,11 +59,7 @@ hipError_t dn_allow_big_lds(const void* kernel, int bytes) {
 }
 
 // XCD grouping policy (common.h). Read per call, never latched: DN_XCD=0 switches it off (A/B runs, tests of the plain mapping).
-int xcd_images_per_group(int n) {
-    const char* v = getenv("DN_XCD");
-    if (v && atoi(v) == 0) return 0;
-    return n >= 8 ? (n + 7) / 8 : 0;
-}
+int xcd_images_per_group(int n) { return dn_knob("DN_XCD", 1) != 0 && n >= 8 ? (n + 7) / 8 : 0; }
 
 struct Layout {
     int n = 0;
@@ -87,6 +83,28 @@ struct GraphKey {
     }
 };
 
+// One kernel launch of the forward over ops [first, first + len). dn_create builds the list once; the workspace layout takes its
+// time steps from it and enqueue walks it.
+struct Launch {
+    enum Kind {
+        SINGLE,         // one op (an SE whose FCs run inside another launch has no kernel of its own: se_host)
+        EXPDW,          // [expand 1x1 ->] depthwise [-> project 1x1 (+ residual)]: the expanded tensor never leaves LDS (expdw.hip)
+        PW_DW,          // depthwise 3x3 computed into the B fragments of its projection (pwdirect.hip pw_dw_direct_kernel)
+        CONV_POOL,      // dense 3x3 conv -> MaxPool2d(2, 2) (convbig.hip)
+        TAIL,           // a linear run of tiny layers, one workgroup per image (tail.hip)
+        HEADS,          // every head op: the fused head launch and / or the grouped launches (run_heads)
+    } kind = SINGLE;
+    int first = 0, len = 1;
+    bool has_expand = false, has_project = false;   // EXPDW
+    int se = -1;            // SINGLE PW / DW: the SE op whose FCs run in its prologue (pointwise.hip SEF) / tail (depthwise.hip dw_se_tail)
+    int se_slot = -1;       // SINGLE DW with se: its slot of the counter block
+    int se_host = -1;       // SINGLE SE: the op whose launch computes it
+    bool stem_split = false;    // SINGLE STEM: may run on the split-fp16 matrix kernel (dn_create checks the host copy of the weights)
+    int stem_scale_log2 = 0;    //   its power-of-two weight scale
+    std::vector<char> materialise;                  // TAIL, per op: its output is read outside the run -> also to HBM
+    std::vector<int> head_dw, head_cls, head_reg;   // HEADS: the depthwise ops, class-head and box-head convs
+};
+
 struct dn_plan {
     dn_model_desc d;
     std::vector<dn_tensor_desc> tensors;
@@ -104,8 +122,6 @@ struct dn_plan {
     bool graph_mode = true;
     std::map<GraphKey, hipGraphExec_t> graphs;
     hipStream_t capture_stream = nullptr;   // capture never happens on the caller's stream (may be the null stream)
-    std::vector<int> op_stream;             // 0 backbone, 1 class-head chain, 2 box-head chain (head ops and the depthwise ops feeding them)
-    std::vector<int> op_wait_level;         // head-chain op reading a feature map: its level, else -1
     int split = 2;                          // sub-batch branches per forward (see batch_split)
     bool ws_reuse = true;                   // DN_WS_REUSE=0: one private block per tensor (every intermediate stays readable after the forward)
     int chain_graphs = -1;                  // DN_CHAIN_GRAPHS: 1 = one single-chain graph per sub-batch on its own stream, 0 = branches of ONE graph, -1 = by batch size
@@ -114,24 +130,11 @@ struct dn_plan {
     hipEvent_t ev_fork = nullptr, ev_branch[3] = {nullptr, nullptr, nullptr};
     std::map<std::pair<int, int>, Layout> sub_layouts;
     int chains_override = 0;                // dn_set_chains: > 0 = that many sub-batch chains per forward whatever the batch size
-    float* packed_out = nullptr;
+    float* packed_out = nullptr;            // optional extra output of the merge kernel (dn_set_packed_output)
     bool input_u8 = false;                  // the current call's images are [n][h][w][3] uint8 (dn_forward_u8)
-    // head ops (dw -> 1x1 / dense 3x3 per level, both heads) run as grouped launches once the backbone is done
-    int head_first = -1;                    // index of the first head-chain op (all later ops are head-chain ops), -1: off
-    std::vector<int> head_dw, head_cls, head_reg;
-    // run of tiny backbone layers [tail_first, tail_end) executed by one per-image workgroup (tail.hip); -1: none
-    int tail_first = -1, tail_end = -1;
-    std::vector<int> se_in_dw;              // per op: DW op -> index of the SE op whose FCs run in its tail (depthwise.hip dw_se_tail), SE op -> -2, else -1
-    int n_se_in_dw = 0;                     // such pairs; slot q of the counter block belongs to the q-th
-    std::vector<int> se_slot;               // per op (DW op of a pair): q
+    std::vector<Launch> launches;           // the forward's kernel launches in order (dn_create), covering every op once
+    int n_se_in_dw = 0;                     // depthwise launches computing an SE in their tail; slot q of the counter block belongs to the q-th
     int post_ticket_slot = -1;              // slot of the counter block lent to launch_postprocess (PostArgs::tickets); needs the stem launch that zeroes the block
-    std::vector<char> stem_split_ok;        // per op: STEM op that may run on the split-fp16 matrix kernel (dn_create checks the host copy of the weights)
-    std::vector<int> stem_scale_log2;       // per op: its power-of-two weight scale
-    std::vector<int> se_fold;               // per op: PW op -> index of the SE op whose FCs run in its prologue (pointwise.hip SEF), SE op -> -2, else -1
-    std::vector<char> tail_materialise;     // per op of the run: its output is read outside the run (pyramid feature) -> also to HBM            // optional extra output of the merge kernel (dn_set_packed_output)
-    // inverted-residual stages that run as one launch (expdw.hip): at the first op of a group, fused_len = number of ops and
-    // fused_kind bit0 = has expand (1x1), bit1 = has project (1x1 [+ residual]); the depthwise op is always part of it
-    std::vector<int> fused_len, fused_kind;
     // profiling
     bool profiling = false;
     std::vector<hipEvent_t> events;
@@ -163,6 +166,26 @@ static int batch_split(const dn_plan* p, int n) {
     return p->split;
 }
 static int sub_count(int n, int S, int k) { const int base = n / S, rem = n % S; return base + (k < rem ? 1 : 0); }
+
+static int level_of(const dn_plan* p, int t) {
+    for (int l = 0; l < p->d.n_levels; ++l) if (p->d.level_tensor[l] == t) return l;
+    return -1;
+}
+static int reads(const dn_op_desc& o, int t) { return (o.in == t) + (o.residual == t) + (o.se == t); }
+// readers of tensor t; a pyramid feature counts 100 more (it must be materialised)
+static int uses(const dn_plan* p, int t) {
+    int u = 0;
+    for (const dn_op_desc& o : p->ops) u += reads(o, t);
+    for (int l = 0; l < p->d.n_levels; ++l) u += p->d.level_tensor[l] == t ? 100 : 0;
+    return u;
+}
+// t is a pyramid feature or read by an op outside [first, end): a launch of those ops must write it to the workspace
+static bool read_outside(const dn_plan* p, int t, int first, int end) {
+    if (level_of(p, t) >= 0) return true;
+    for (int u = 0; u < (int)p->ops.size(); ++u)
+        if ((u < first || u >= end) && reads(p->ops[u], t)) return true;
+    return false;
+}
 
 static const Layout& get_layout(dn_plan* p, int n) {
     auto it = p->layouts.find(n);
@@ -196,53 +219,33 @@ static const Layout& get_layout(dn_plan* p, int n) {
         // addressing disjoint rows of the same blocks. 2.6 GB -> ~0.4 GB at batch 64: producer -> consumer pairs of the large maps
         // now rewrite lines that are already resident in the Infinity Cache instead of streaming through fresh memory.
         const int NO = (int)p->ops.size();
-        std::vector<int> when(NO);                 // launch time step of every op
+        std::vector<int> when(NO);                 // launch time step of every op: the index of its launch
         std::vector<char> inner(T, 0);             // tensor produced AND consumed inside one fused launch (never materialised)
-        {
-            int tstep = 0;
-            for (int i = 0; i < NO;) {
-                int len = 1;
-                if (p->head_first >= 0 && i >= p->head_first) {
-                    // head launches: the depthwise group, then the 1x1 / dense group(s)
-                    for (int q = i; q < NO; ++q) when[q] = tstep + (p->ops[q].type == DN_OP_DW ? 0 : 1);
-                    break;
-                }
-                if (i == p->tail_first) len = p->tail_end - p->tail_first;
-                else if (p->fused_len[i] > 0) len = p->fused_len[i];
-                for (int q = 0; q < len; ++q) when[i + q] = tstep;
-                if (len > 1) {
-                    for (int q = 0; q + 1 < len; ++q) {
-                        const int tid = p->ops[i + q].out;
-                        bool keep = false;
-                        if (i == p->tail_first) keep = p->tail_materialise[q] != 0;
-                        for (int l = 0; l < p->d.n_levels; ++l) keep |= p->d.level_tensor[l] == tid;
-                        for (int u = 0; u < NO; ++u) {
-                            if (u >= i && u < i + len) continue;
-                            const dn_op_desc& o = p->ops[u];
-                            keep |= (o.in == tid || o.residual == tid || o.se == tid);
-                        }
-                        if (!keep) inner[tid] = 1;
-                    }
-                }
-                ++tstep;
-                i += len;
-            }
+        for (size_t t = 0; t < p->launches.size(); ++t) {
+            const Launch& l = p->launches[t];
+            const int end = l.first + l.len;
+            // head launches: the depthwise group, then the 1x1 / dense group(s)
+            for (int q = l.first; q < end; ++q) when[q] = (int)t + (l.kind == Launch::HEADS && p->ops[q].type != DN_OP_DW ? 1 : 0);
+            if (l.kind != Launch::HEADS)
+                for (int q = l.first; q + 1 < end; ++q)
+                    if (!read_outside(p, p->ops[q].out, l.first, end)) inner[p->ops[q].out] = 1;
         }
         std::vector<int> born(T, -1), dies(T, -1);
         for (int i = 0; i < NO; ++i) {
             const dn_op_desc& o = p->ops[i];
             auto use = [&](int tid) { if (tid >= 0) dies[tid] = std::max(dies[tid], when[i]); };
             use(o.in); use(o.residual); use(o.se);
-            if (p->se_fold[i] >= 0) use(p->ops[p->se_fold[i]].in);       // folded squeeze-excitation: the projection reads the pooled partial sums
             if (born[o.out] < 0) born[o.out] = when[i];
             dies[o.out] = std::max(dies[o.out], when[i]);
             if (o.pool >= 0) { if (born[o.pool] < 0) born[o.pool] = when[i]; dies[o.pool] = std::max(dies[o.pool], when[i]); }
         }
-        for (int i = 0; i < NO; ++i)
-            if (p->se_in_dw[i] >= 0) {      // the scale vector is written by the depthwise launch itself (dw_se_tail)
-                const int t = p->ops[p->se_in_dw[i]].out;
-                if (born[t] >= 0) born[t] = std::min(born[t], when[i]);
-            }
+        for (const Launch& l : p->launches) {
+            if (l.se < 0) continue;
+            const dn_op_desc& so = p->ops[l.se];
+            const int t = when[l.first];
+            if (p->ops[l.first].type == DN_OP_PW) dies[so.in] = std::max(dies[so.in], t);      // folded SE: the projection reads the pooled partial sums
+            else if (born[so.out] >= 0) born[so.out] = std::min(born[so.out], t);                // dw_se_tail: the depthwise launch writes the scale vector
+        }
         const int t_end = NO + 2;
         for (int l = 0; l < p->d.n_levels; ++l) dies[p->d.level_tensor[l]] = t_end;      // read back by tests / callers after the forward
         struct Blk { size_t off, bytes; int born, dies; };
@@ -291,6 +294,264 @@ static const Layout& get_layout(dn_plan* p, int n) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// the launch list: dn_create's grouping passes work on one Launch per op. at[i].len > 0: a launch starts at op i; len == 0: op i
+// belongs to an earlier op's launch.
+using OpLaunches = std::vector<Launch>;
+
+static bool plain(const OpLaunches& at, int i) { return at[i].kind == Launch::SINGLE && at[i].len == 1; }
+
+static Launch& group(OpLaunches& at, int first, Launch::Kind kind, int len) {
+    at[first] = Launch();
+    at[first].kind = kind; at[first].first = first; at[first].len = len;
+    for (int q = 1; q < len; ++q) at[first + q].len = 0;
+    return at[first];
+}
+
+static bool plain_pw(const dn_op_desc& o) { return o.type == DN_OP_PW && !o.head && o.se < 0; }
+static bool plain_dw(const dn_op_desc& o) { return o.type == DN_OP_DW && !o.head && o.dil == 1; }
+
+// expand (1x1) -> depthwise [-> project] at op i whose expanded tensor has no other reader: the ops of one EXPDW launch, 0: none.
+// The project stage (whole inverted-residual block in one launch) goes down to the 20 x 20 maps: one workgroup owns all expanded
+// channels of its pixel tile (chunk loop), the expand's A fragments fit the register variants up to cin = 88, and the (pixel tile x
+// channel tile) units of the projection must fit the 8 waves (5 x 10 pixel tiles there). Measured: the 160^2 / 80^2 blocks
+// -20 % each (round 1); the four blocks without squeeze-excitation on the 20 x 20 maps (40->240->80 stride 2, 80->200->80,
+// 2 x 80->184->80: three launches of 5 - 11 us each become one of 11 - 17 us) batch 64 1.10 -> 1.055 ms, batch 32 0.765 -> 0.74
+static int expdw_len(const dn_plan* p, int i) {
+    const int max_hw = dn_knob("DN_EXPDW_MAXHW", 1 << 30);
+    // measured per layer (bench.py --per-op, tools/probe_expdw.py): the fused kernel currently wins on the large maps only
+    const int min_hw = dn_knob("DN_EXPDW_MINHW", 6400);
+    const int proj_min_hw = dn_knob("DN_EXPDW_PROJ_MINHW", 300);      // (19 x 19 maps of the 300-pixel models included)
+    const dn_op_desc& a = p->ops[i];
+    const dn_op_desc& d = p->ops[i + 1];
+    if (!(plain_pw(a) && a.residual < 0 && uses(p, a.out) == 1 && plain_dw(d) && d.in == a.out && p->tensors[a.in].kind == DN_T_ACT &&
+          expdw_supported(a.cin, a.cout, d.k, d.stride)))
+        return 0;
+    const dn_tensor_desc& to = p->tensors[d.out];
+    if (to.h * to.w > max_hw) return 0;
+    bool can_proj = i + 2 < (int)p->ops.size() && a.cin <= 96;
+    if (can_proj) {
+        const dn_op_desc& pj = p->ops[i + 2];
+        can_proj = plain_pw(pj) && pj.in == d.out && uses(p, d.out) == 1 && d.pool < 0 && pj.act == DN_ACT_NONE && d.cin <= 640 &&
+                   to.h * to.w >= proj_min_hw && expdw_project_supported(d.cin, pj.cout, to.h, to.w, d.stride) &&
+                   (pj.residual < 0 || (pj.residual == a.in && d.stride == 1 && pj.cout == p->tensors[a.in].c));
+    }
+    if (to.h * to.w < min_hw && !can_proj) return 0;      // below the expand+depthwise threshold only whole blocks fuse
+    return can_proj ? 3 : 2;
+}
+
+// depthwise 3x3 -> project without an expand at op i (first block of the MobileNets, 16 / 32 channels on the largest map): the
+// depthwise is computed straight into the projection's B fragments (measured: V3's 16-channel block batch 64 0.782 -> 0.765 ms in
+// flight, 1.035 -> 1.02 one at a time; the 32-channel block of the V2 model at 300 x 300 level with the two launches -- two K steps
+// of nine taps per lane for a projection that fills half a tile: DN_PW_DW=2 only). (The same pair through the LDS-tiled block
+// kernel was correct but slower than the two launches -- 16 channels leave half of the workgroup idle in the depthwise stage -- and
+// is not dispatched.)
+static bool pw_dw_at(const dn_plan* p, int i, int mode) {
+    const dn_op_desc& a = p->ops[i];
+    const dn_op_desc& d = p->ops[i + 1];
+    const dn_tensor_desc& ti = p->tensors[a.in];
+    return mode && plain_dw(a) && a.k == 3 && a.stride == 1 && a.pad == 1 && a.pool < 0 && (a.cin == 16 || (a.cin == 32 && mode == 2)) &&
+           ti.kind == DN_T_ACT && plain_pw(d) && d.in == a.out && uses(p, a.out) == 1 && d.cout <= 32 && d.cout % 8 == 0 &&
+           (d.residual < 0 || (d.residual == a.in && d.cout == a.cin)) && ti.h * ti.w >= 32 &&
+           fd_ok((unsigned long long)ti.h * ti.w, (unsigned)ti.w);      // (the kernel's x = pixel % w)
+}
+
+// ---- inverted-residual blocks: EXPDW and PW_DW launches, claimed left to right (the first that matches at an op wins).
+//      DN_EXPDW=0 turns both off.
+static void group_inverted_residuals(dn_plan* p, OpLaunches& at) {
+    if (!dn_knob("DN_EXPDW", 1)) return;
+    const int pw_dw = dn_knob("DN_PW_DW", 1);
+    for (int i = 0; i + 1 < (int)p->ops.size(); ++i) {
+        if (const int len = expdw_len(p, i)) {
+            Launch& l = group(at, i, Launch::EXPDW, len);
+            l.has_expand = true;
+            l.has_project = len == 3;
+            i += len - 1;
+        } else if (pw_dw_at(p, i, pw_dw)) {
+            group(at, i, Launch::PW_DW, 2);
+            ++i;
+        }
+    }
+}
+
+// ---- dense 3x3 conv -> MaxPool2d(2, 2) pairs (VGG conv1_2 / conv2_2): one launch (convbig.hip conv_patch_kernel)
+static void group_conv_pool(dn_plan* p, OpLaunches& at) {
+    for (int i = 0; i + 1 < (int)p->ops.size(); ++i) {
+        const dn_op_desc& c = p->ops[i];
+        const dn_op_desc& m = p->ops[i + 1];
+        const dn_tensor_desc& tc = p->tensors[c.out];
+        if (c.type == DN_OP_CONV && !c.head && c.k == 3 && c.stride == 1 && c.pad == 1 && c.dil == 1 && m.type == DN_OP_MAXPOOL && m.in == c.out &&
+            m.k == 2 && m.stride == 2 && m.pad == 0 && plain(at, i) && p->tensors[c.in].h == tc.h &&
+            ((uses(p, c.out) == 1 && conv_pool_ok(c.cin, c.cout, tc.h, tc.w)) ||
+             (!conv_patch_pool_ok(c.cin, c.cout, tc.h, tc.w) && conv_halo_pool_ok(c.cin, c.cout, tc.h, tc.w)))) {      // (the run-staged tile can write both maps)
+            group(at, i, Launch::CONV_POOL, 2);
+            ++i;
+        }
+    }
+}
+
+// ---- stems: the split-fp16 matrix kernel (depthwise.hip stem_split_kernel) takes weights and bias scaled by a power of two such that the
+//      largest magnitude lands in [2^13, 2^15) (the low halves of the split then stay normal fp16 numbers), and a normalised image that fp16 holds
+//      (pixels in [0, 1]: |x| <= max(mean, 1 - mean) / std)
+static void check_stems(const dn_plan* p, const void* weights, OpLaunches& at) {
+    for (int i = 0; i < (int)p->ops.size(); ++i) {
+        const dn_op_desc& so = p->ops[i];
+        if (so.type != DN_OP_STEM) continue;
+        const float* hw = reinterpret_cast<const float*>(static_cast<const unsigned char*>(weights) + so.w_off);
+        const float* hb = reinterpret_cast<const float*>(static_cast<const unsigned char*>(weights) + so.b_off);
+        bool ok = true;
+        float big = 0.f;
+        for (int q = 0; q < so.k * so.k * 3 * so.cout; ++q) { ok = ok && std::isfinite(hw[q]); big = std::max(big, std::fabs(hw[q])); }
+        for (int q = 0; q < so.cout; ++q) { ok = ok && std::isfinite(hb[q]); big = std::max(big, std::fabs(hb[q])); }
+        for (int c = 0; c < 3; ++c) ok = ok && p->d.std[c] > 0.f && std::max(std::fabs(p->d.mean[c]), std::fabs(1.f - p->d.mean[c])) / p->d.std[c] < 3.0e4f;
+        int e = 0;
+        if (ok && big > 0.f) {
+            (void)std::frexp(big, &e);           // big = m 2^e, m in [0.5, 1)
+            e = 15 - e;                          // big 2^e in [2^14, 2^15)
+            e = std::max(-100, std::min(100, e));
+        }
+        at[i].stem_split = ok;
+        at[i].stem_scale_log2 = e;
+    }
+}
+
+// ---- small squeeze-excitations (c <= 128, squeeze <= 32: the 40 x 40 blocks of MobileNetV3) are computed in the prologue of the
+//      projection that consumes them: one dependent launch (~10 us of pure latency) less per block
+static void fold_se_into_projections(const dn_plan* p, OpLaunches& at) {
+    const bool se_small = dn_knob("DN_SE_SMALL", 1) != 0;
+    for (int i = 0; i + 1 < (int)p->ops.size(); ++i) {
+        const dn_op_desc& so = p->ops[i];
+        const dn_op_desc& pj = p->ops[i + 1];
+        if (so.type != DN_OP_SE || pj.type != DN_OP_PW || pj.se != so.out || pj.head) continue;
+        const dn_tensor_desc& ti = p->tensors[pj.in];
+        const auto users = std::count_if(p->ops.begin(), p->ops.end(), [&](const dn_op_desc& o) { return o.se == so.out; });
+        if (users == 1 && pw_se_fold_supported(pj.cin, pj.cout, so.squeeze, ti.h * ti.w)) {
+            // DN_SE_SMALL (default 1, see below): these small FCs go to the tail of the pooling depthwise launch instead and the projection runs
+            // on the register-direct kernel with the scale applied to its x fragments
+            if (se_small && (ti.h * ti.w) % 32 == 0 && pj.cin <= 128 && depthwise_se_tail_supported(so.cin, so.squeeze)) continue;
+            at[i].se_host = i + 1;
+            at[i + 1].se = i;
+        }
+    }
+}
+
+// ---- the other squeeze-excitations (opt-in, DN_SE_IN_DW=1): their FCs run in the tail of the depthwise launch that pools for
+//      them (the last workgroup of an image to finish; depthwise.hip dw_se_tail) instead of a 32-workgroup launch of their own.
+//      Needs the plain depthwise launch (not the fused expand+depthwise or tail runs) and the stem launch, which clears
+//      the counters. MEASURED and left off. With a device-scope fence per workgroup the 20 x 20 depthwise launches went from
+//      10 to 50 us (a release at agent scope writes back the XCD's L2: batch 64 1.12 -> 1.32 ms). With the fence-free publish
+//      (device-scope atomic stores / loads of the partial sums, relaxed ticket) the launch overhead is gone, but the FCs of the
+//      large blocks stream 230 - 450 KB of weights into ONE compute unit per image on 256 threads: batch 64 1.063 -> 1.068 ms.
+//      DN_SE_SMALL=1 does the same for the small squeeze-excitations only (instead of folding them into the projection's
+//      prologue), the projection then runs on the register-direct kernel with the scale applied to its x fragments:
+//      1.063 -> 1.054 ms at batch 64, no change at 32 / 16 one forward at a time; with three forwards in flight (pipeline.py)
+//      0.840 -> 0.825 ms at batch 64 and 0.463 -> 0.458 ms at 32: on by default.
+static void se_in_depthwise_tails(dn_plan* p, OpLaunches& at) {
+    const bool all = dn_knob("DN_SE_IN_DW", 0) != 0;
+    if ((!all && !dn_knob("DN_SE_SMALL", 1)) || p->ops[0].type != DN_OP_STEM) return;
+    for (int i = 1; i < (int)p->ops.size(); ++i) {
+        const dn_op_desc& so = p->ops[i];
+        if (so.type != DN_OP_SE || at[i].se_host >= 0) continue;
+        if (!all && !(so.cin <= 128 && so.squeeze <= 32)) continue;      // DN_SE_SMALL alone: the small ones only
+        int j = -1;
+        for (int q = 0; q < i; ++q) if (p->ops[q].type == DN_OP_DW && p->ops[q].pool == so.in) j = q;
+        if (j < 1 || !depthwise_se_tail_supported(so.cin, so.squeeze) || !plain(at, j)) continue;
+        at[j].se = i;
+        at[j].se_slot = p->n_se_in_dw++;
+        at[i].se_host = j;
+    }
+}
+
+// partial-sum rows of every pooled tensor = workgroups per image of its producing depthwise op
+static void size_pool_partials(dn_plan* p, const OpLaunches& at) {
+    p->pool_blocks.assign(p->tensors.size(), 0);
+    for (int i = 0; i < (int)p->ops.size(); ++i) {
+        const dn_op_desc& o = p->ops[i];
+        if (o.type != DN_OP_DW || o.pool < 0) continue;
+        const dn_tensor_desc& ti = p->tensors[o.in];
+        const dn_tensor_desc& to = p->tensors[o.out];
+        if (i > 0 && at[i - 1].kind == Launch::EXPDW && at[i - 1].has_expand) {
+            p->pool_blocks[o.pool] = expdw_tiles_per_image(to.h, to.w, o.stride);
+            continue;
+        }
+        DwArgs a{};
+        a.n = 1; a.h = ti.h; a.w_ = ti.w; a.c = o.cin; a.k = o.k; a.stride = o.stride; a.pad = o.pad; a.ho = to.h; a.wo = to.w;
+        a.pool = reinterpret_cast<float*>(1);      // (geometry only: a pooling launch)
+        p->pool_blocks[o.pool] = depthwise_pool_blocks(a);
+    }
+}
+
+// ---- heads: once the backbone is done, every remaining op is a head op of the pyramid levels (dw -> 1x1 / dense 3x3 per level,
+//      both heads) and they run as one HEADS launch group. Returns its first op (ops.size(): none).
+static int group_heads(const dn_plan* p, OpLaunches& at) {
+    const int N = (int)p->ops.size();
+    // head chain: a head conv, or the op producing its (non-pyramid) input
+    auto head_chain = [&](int i) {
+        const dn_op_desc& o = p->ops[i];
+        if (o.head) return true;
+        for (const dn_op_desc& u : p->ops) if (u.head && u.in == o.out && level_of(p, o.out) < 0) return true;
+        return false;
+    };
+    int first = -1, last_main = -1;
+    for (int i = 0; i < N; ++i) {
+        if (!head_chain(i)) last_main = i;
+        else if (first < 0) first = i;
+    }
+    if (!dn_knob("DN_HEAD_GROUPS", 1) || first < 0 || first < last_main) return N;
+    Launch h;
+    int kinds = 0;
+    for (int i = first; i < N; ++i) {
+        const dn_op_desc& o = p->ops[i];
+        const dn_op_desc& f = p->ops[first];
+        if (o.type == DN_OP_DW) {
+            if (o.pool >= 0 || o.k != f.k || o.stride != f.stride || f.type != DN_OP_DW || level_of(p, o.in) < 0) return N;
+            h.head_dw.push_back(i);
+        } else if ((o.type == DN_OP_PW || o.type == DN_OP_CONV) && o.head) {
+            kinds |= (o.type == DN_OP_PW) ? 1 : 2;
+            (o.head == 1 ? h.head_cls : h.head_reg).push_back(i);
+        } else return N;
+    }
+    if (kinds == 3 || h.head_dw.size() > 12 || h.head_cls.size() > 8 || h.head_reg.size() > 8 || h.head_cls.empty()) return N;
+    Launch& l = group(at, first, Launch::HEADS, N - first);
+    l.head_dw.swap(h.head_dw); l.head_cls.swap(h.head_cls); l.head_reg.swap(h.head_reg);
+    return first;
+}
+
+// ---- tail run: the longest suffix of the backbone (ops [.., end) before the heads) that is a linear chain of tiny layers
+static void group_tail(const dn_plan* p, OpLaunches& at, int end) {
+    if (!dn_knob("DN_TAIL", 1)) return;
+    int first = end;
+    while (first > 0) {
+        const int i = first - 1;
+        const dn_op_desc& o = p->ops[i];
+        const dn_tensor_desc& ti = p->tensors[o.in];
+        const dn_tensor_desc& to = p->tensors[o.out];
+        if (!plain(at, i) || ti.kind != DN_T_ACT || !tail_op_supported(o, ti.h, ti.w, to.h, to.w)) break;
+        if (first < end && p->ops[first].in != o.out) break;         // must feed the next op of the run
+        --first;
+    }
+    first = std::max(first, end - TAIL_MAX_OPS);
+    if (end - first < 2) return;
+    Launch& l = group(at, first, Launch::TAIL, end - first);
+    for (int i = first; i < end; ++i) l.materialise.push_back(read_outside(p, p->ops[i].out, first, end) ? 1 : 0);
+}
+
+static void plan_launches(dn_plan* p, const void* weights) {
+    const int N = (int)p->ops.size();
+    OpLaunches at(N);
+    for (int i = 0; i < N; ++i) at[i].first = i;
+    group_inverted_residuals(p, at);
+    group_conv_pool(p, at);
+    check_stems(p, weights, at);
+    fold_se_into_projections(p, at);
+    se_in_depthwise_tails(p, at);
+    for (int i = 0; i < N; ++i)
+        if (p->ops[i].type == DN_OP_STEM) { p->post_ticket_slot = p->n_se_in_dw++; break; }
+    size_pool_partials(p, at);
+    group_tail(p, at, group_heads(p, at));
+    p->launches.clear();
+    for (Launch& l : at) if (l.len > 0) p->launches.push_back(std::move(l));
+}
+
 extern "C" int dn_create(const dn_model_desc* desc, const void* weights, size_t weight_bytes, dn_plan** out) {
     DN_REQUIRE(desc && weights && out, "dn_create: null argument");
     DN_REQUIRE(desc->abi_version == DN_ABI_VERSION, "dn_create: ABI version %d != library %d", desc->abi_version, DN_ABI_VERSION);
@@ -319,262 +580,12 @@ extern "C" int dn_create(const dn_model_desc* desc, const void* weights, size_t 
         if (o.type < DN_OP_STEM || o.type > DN_OP_L2NORM) { dn_set_error("dn_create: op %d unknown type %d", i, o.type); return fail(DN_E_INVALID); }
         if (o.head && (o.level < 0 || o.level >= desc->n_levels)) { dn_set_error("dn_create: head op %d bad level", i); return fail(DN_E_INVALID); }
     }
-    // ---- expand (1x1) -> depthwise pairs whose expanded tensor has no other reader: one launch, the tensor never leaves LDS
-    p->fused_len.assign(desc->n_ops, 0);
-    p->fused_kind.assign(desc->n_ops, 0);
-    {
-        const bool enabled = getenv("DN_EXPDW") ? atoi(getenv("DN_EXPDW")) != 0 : true;
-        const int max_hw = getenv("DN_EXPDW_MAXHW") ? atoi(getenv("DN_EXPDW_MAXHW")) : (1 << 30);
-        // measured per layer (bench.py --per-op, tools/probe_expdw.py): the fused kernel currently wins on the large maps only
-        const int min_hw = getenv("DN_EXPDW_MINHW") ? atoi(getenv("DN_EXPDW_MINHW")) : 6400;
-        std::vector<int> uses(desc->n_tensors, 0);
-        for (int i = 0; i < desc->n_ops; ++i) {
-            const dn_op_desc& o = p->ops[i];
-            uses[o.in]++;
-            if (o.residual >= 0) uses[o.residual]++;
-            if (o.se >= 0) uses[o.se]++;
-        }
-        for (int l = 0; l < desc->n_levels; ++l) uses[desc->level_tensor[l]] += 100;    // features must be materialised
-        // project stage (whole inverted-residual block in one launch) down to the 20 x 20 maps: one workgroup owns all expanded channels
-        // of its pixel tile (chunk loop), the expand's A fragments fit the register variants up to cin = 88, and the (pixel tile x
-        // channel tile) units of the projection must fit the 8 waves (5 x 10 pixel tiles there). Measured: the 160^2 / 80^2 blocks
-        // -20 % each (round 1); the four blocks without squeeze-excitation on the 20 x 20 maps (40->240->80 stride 2, 80->200->80,
-        // 2 x 80->184->80: three launches of 5 - 11 us each become one of 11 - 17 us) batch 64 1.10 -> 1.055 ms, batch 32 0.765 -> 0.74
-        const int proj_min_hw = getenv("DN_EXPDW_PROJ_MINHW") ? atoi(getenv("DN_EXPDW_PROJ_MINHW")) : 300;      // (19 x 19 maps of the 300-pixel models included)
-        auto plain_pw = [&](const dn_op_desc& o) { return o.type == DN_OP_PW && !o.head && o.se < 0; };
-        auto dw_ok = [&](const dn_op_desc& o) { return o.type == DN_OP_DW && !o.head && o.dil == 1; };
-        auto proj_ok = [&](const dn_op_desc& pj, const dn_op_desc& d, int block_in) {
-            const dn_tensor_desc& to = p->tensors[d.out];
-            return plain_pw(pj) && pj.in == d.out && uses[d.out] == 1 && d.pool < 0 && pj.act == DN_ACT_NONE && d.cin <= 640 &&
-                   to.h * to.w >= proj_min_hw && expdw_project_supported(d.cin, pj.cout, to.h, to.w, d.stride) &&
-                   (pj.residual < 0 || (pj.residual == block_in && d.stride == 1 && pj.cout == p->tensors[block_in].c));
-        };
-        for (int i = 0; enabled && i + 1 < desc->n_ops; ++i) {
-            const dn_op_desc& a = p->ops[i];
-            const dn_op_desc& d = p->ops[i + 1];
-            if (plain_pw(a) && a.residual < 0 && uses[a.out] == 1 && dw_ok(d) && d.in == a.out && p->tensors[a.in].kind == DN_T_ACT &&
-                expdw_supported(a.cin, a.cout, d.k, d.stride)) {
-                const dn_tensor_desc& to = p->tensors[d.out];
-                if (to.h * to.w > max_hw) continue;
-                const bool can_proj = i + 2 < desc->n_ops && a.cin <= 96 && proj_ok(p->ops[i + 2], d, a.in);
-                if (to.h * to.w < min_hw && !can_proj) continue;      // below the expand+depthwise threshold only whole blocks fuse
-                if (can_proj) {
-                    p->fused_len[i] = 3; p->fused_kind[i] = 3; i += 2;
-                } else {
-                    p->fused_len[i] = 2; p->fused_kind[i] = 1; i += 1;
-                }
-                continue;
-            }
-            // depthwise 3x3 -> project without an expand (first block of the MobileNets, 16 / 32 channels on the largest map): the
-            // depthwise is computed straight into the projection's B fragments (pwdirect.hip pw_dw_direct_kernel), fused_kind 8
-            // (measured: V3's 16-channel block batch 64 0.782 -> 0.765 ms in flight, 1.035 -> 1.02 one at a time; the 32-channel block of the V2
-            // model at 300 x 300 level with the two launches -- two K steps of nine taps per lane for a projection that fills half a tile: DN_PW_DW=2 only)
-            if (dn_knob("DN_PW_DW", 1) && dw_ok(a) && a.k == 3 && a.stride == 1 && a.pad == 1 && a.pool < 0 && (a.cin == 16 || (a.cin == 32 && dn_knob("DN_PW_DW", 1) == 2)) &&
-                p->tensors[a.in].kind == DN_T_ACT && plain_pw(d) && d.in == a.out && uses[a.out] == 1 && d.cout <= 32 && d.cout % 8 == 0 &&
-                (d.residual < 0 || (d.residual == a.in && d.cout == a.cin)) && p->tensors[a.in].h * p->tensors[a.in].w >= 32 &&
-                fd_ok((unsigned long long)p->tensors[a.in].h * p->tensors[a.in].w, (unsigned)p->tensors[a.in].w)) {      // (the kernel's x = pixel % w)
-                p->fused_len[i] = 2; p->fused_kind[i] = 8; i += 1;
-                continue;
-            }
-            // (the same pair through the LDS-tiled block kernel was correct but slower than the two launches -- 16 channels leave half of the
-            //  workgroup idle in the depthwise stage -- and is not dispatched)
-        }
-    }
-    // ---- dense 3x3 conv -> MaxPool2d(2, 2) pairs (VGG conv1_2 / conv2_2): one launch, fused_kind 4 (convbig.hip conv_patch_kernel)
-    {
-        std::vector<int> uses(desc->n_tensors, 0);
-        for (int i = 0; i < desc->n_ops; ++i) {
-            const dn_op_desc& o = p->ops[i];
-            uses[o.in]++;
-            if (o.residual >= 0) uses[o.residual]++;
-            if (o.se >= 0) uses[o.se]++;
-        }
-        for (int l = 0; l < desc->n_levels; ++l) uses[desc->level_tensor[l]] += 100;
-        for (int i = 0; i + 1 < desc->n_ops; ++i) {
-            const dn_op_desc& c = p->ops[i];
-            const dn_op_desc& m = p->ops[i + 1];
-            const dn_tensor_desc& tc = p->tensors[c.out];
-            if (c.type == DN_OP_CONV && !c.head && c.k == 3 && c.stride == 1 && c.pad == 1 && c.dil == 1 && m.type == DN_OP_MAXPOOL && m.in == c.out &&
-                m.k == 2 && m.stride == 2 && m.pad == 0 && p->fused_len[i] == 0 && p->tensors[c.in].h == tc.h &&
-                ((uses[c.out] == 1 && conv_pool_ok(c.cin, c.cout, tc.h, tc.w)) ||
-                 (!conv_patch_pool_ok(c.cin, c.cout, tc.h, tc.w) && conv_halo_pool_ok(c.cin, c.cout, tc.h, tc.w)))) {      // (the run-staged tile can write both maps)
-                p->fused_len[i] = 2;
-                p->fused_kind[i] = 4;
-                ++i;
-            }
-        }
-    }
-    // ---- small squeeze-excitations (c <= 128, squeeze <= 32: the 40 x 40 blocks of MobileNetV3) are computed in the prologue of the
-    //      projection that consumes them: one dependent launch (~10 us of pure latency) less per block
-    // ---- stems: the split-fp16 matrix kernel (depthwise.hip stem_split_kernel) takes weights and bias scaled by a power of two such that the
-    //      largest magnitude lands in [2^13, 2^15) (the low halves of the split then stay normal fp16 numbers), and a normalised image that fp16 holds
-    //      (pixels in [0, 1]: |x| <= max(mean, 1 - mean) / std)
-    p->stem_split_ok.assign(desc->n_ops, 0);
-    p->stem_scale_log2.assign(desc->n_ops, 0);
-    for (int i = 0; i < desc->n_ops; ++i) {
-        const dn_op_desc& so = p->ops[i];
-        if (so.type != DN_OP_STEM) continue;
-        const float* hw = reinterpret_cast<const float*>(static_cast<const unsigned char*>(weights) + so.w_off);
-        const float* hb = reinterpret_cast<const float*>(static_cast<const unsigned char*>(weights) + so.b_off);
-        bool ok = true;
-        float big = 0.f;
-        for (int q = 0; q < so.k * so.k * 3 * so.cout; ++q) { ok = ok && std::isfinite(hw[q]); big = std::max(big, std::fabs(hw[q])); }
-        for (int q = 0; q < so.cout; ++q) { ok = ok && std::isfinite(hb[q]); big = std::max(big, std::fabs(hb[q])); }
-        for (int c = 0; c < 3; ++c) ok = ok && desc->std[c] > 0.f && std::max(std::fabs(desc->mean[c]), std::fabs(1.f - desc->mean[c])) / desc->std[c] < 3.0e4f;
-        int e = 0;
-        if (ok && big > 0.f) {
-            (void)std::frexp(big, &e);           // big = m 2^e, m in [0.5, 1)
-            e = 15 - e;                          // big 2^e in [2^14, 2^15)
-            e = std::max(-100, std::min(100, e));
-        }
-        p->stem_split_ok[i] = ok ? 1 : 0;
-        p->stem_scale_log2[i] = e;
-    }
-    p->se_fold.assign(desc->n_ops, -1);
-    for (int i = 0; i + 1 < desc->n_ops; ++i) {
-        const dn_op_desc& so = p->ops[i];
-        const dn_op_desc& pj = p->ops[i + 1];
-        if (so.type != DN_OP_SE || pj.type != DN_OP_PW || pj.se != so.out || pj.head) continue;
-        const dn_tensor_desc& ti = p->tensors[pj.in];
-        int users = 0;
-        for (int q = 0; q < desc->n_ops; ++q) users += p->ops[q].se == so.out;
-        if (users == 1 && pw_se_fold_supported(pj.cin, pj.cout, so.squeeze, ti.h * ti.w)) {
-            // DN_SE_SMALL (default 1, see below): these small FCs go to the tail of the pooling depthwise launch instead and the projection runs
-            // on the register-direct kernel with the scale applied to its x fragments
-            if (dn_knob("DN_SE_SMALL", 1) && (ti.h * ti.w) % 32 == 0 && pj.cin <= 128 && depthwise_se_tail_supported(so.cin, so.squeeze)) continue;
-            p->se_fold[i] = -2;
-            p->se_fold[i + 1] = i;
-        }
-    }
-    // ---- the other squeeze-excitations (opt-in, DN_SE_IN_DW=1): their FCs run in the tail of the depthwise launch that pools for
-    //      them (the last workgroup of an image to finish; depthwise.hip dw_se_tail) instead of a 32-workgroup launch of their own.
-    //      Needs the plain depthwise launch (not the fused expand+depthwise or tail runs) and the stem launch, which clears
-    //      the counters. MEASURED and left off. With a device-scope fence per workgroup the 20 x 20 depthwise launches went from
-    //      10 to 50 us (a release at agent scope writes back the XCD's L2: batch 64 1.12 -> 1.32 ms). With the fence-free publish
-    //      (device-scope atomic stores / loads of the partial sums, relaxed ticket) the launch overhead is gone, but the FCs of the
-    //      large blocks stream 230 - 450 KB of weights into ONE compute unit per image on 256 threads: batch 64 1.063 -> 1.068 ms.
-    //      DN_SE_SMALL=1 does the same for the small squeeze-excitations only (instead of folding them into the projection's
-    //      prologue), the projection then runs on the register-direct kernel with the scale applied to its x fragments:
-    //      1.063 -> 1.054 ms at batch 64, no change at 32 / 16 one forward at a time; with three forwards in flight (pipeline.py)
-    //      0.840 -> 0.825 ms at batch 64 and 0.463 -> 0.458 ms at 32: on by default.
-    p->se_in_dw.assign(desc->n_ops, -1);
-    p->se_slot.assign(desc->n_ops, -1);
-    p->n_se_in_dw = 0;
-    if ((dn_knob("DN_SE_IN_DW", 0) != 0 || dn_knob("DN_SE_SMALL", 1) != 0) && p->ops[0].type == DN_OP_STEM) {
-        for (int i = 1; i < desc->n_ops; ++i) {
-            const dn_op_desc& so = p->ops[i];
-            if (so.type != DN_OP_SE || p->se_fold[i] == -2) continue;
-            if (!dn_knob("DN_SE_IN_DW", 0) && !(so.cin <= 128 && so.squeeze <= 32)) continue;      // DN_SE_SMALL alone: the small ones only
-            int j = -1;
-            for (int q = 0; q < i; ++q) if (p->ops[q].type == DN_OP_DW && p->ops[q].pool == so.in) j = q;
-            if (j < 1 || !depthwise_se_tail_supported(so.cin, so.squeeze)) continue;
-            bool plain = p->fused_len[j] == 0 && !(p->fused_len[j - 1] >= 2);
-            if (j >= 2 && p->fused_len[j - 2] >= 3) plain = false;
-            if (!plain) continue;
-            p->se_in_dw[j] = i;
-            p->se_in_dw[i] = -2;
-            p->se_slot[j] = p->n_se_in_dw++;
-        }
-    }
-    p->post_ticket_slot = -1;
-    for (int i = 0; i < desc->n_ops; ++i)
-        if (p->ops[i].type == DN_OP_STEM) { p->post_ticket_slot = p->n_se_in_dw++; break; }
-    // partial-sum rows of every pooled tensor = workgroups per image of its producing depthwise op
-    p->pool_blocks.assign(desc->n_tensors, 0);
-    for (int i = 0; i < desc->n_ops; ++i) {
-        const dn_op_desc& o = p->ops[i];
-        if (o.type == DN_OP_DW && o.pool >= 0 && i > 0 && p->fused_len[i - 1] >= 2 && (p->fused_kind[i - 1] & 1)) {
-            const dn_tensor_desc& to = p->tensors[o.out];
-            p->pool_blocks[o.pool] = expdw_tiles_per_image(to.h, to.w, o.stride);
-            continue;
-        }
-        if (o.type == DN_OP_DW && o.pool >= 0) {
-            const dn_tensor_desc& ti = p->tensors[o.in];
-            const dn_tensor_desc& to = p->tensors[o.out];
-            DwArgs a{};
-            a.n = 1; a.h = ti.h; a.w_ = ti.w; a.c = o.cin; a.k = o.k; a.stride = o.stride; a.pad = o.pad; a.ho = to.h; a.wo = to.w;
-            a.pool = reinterpret_cast<float*>(1);      // (geometry only: a pooling launch)
-            p->pool_blocks[o.pool] = depthwise_pool_blocks(a);
-        }
-    }
-    // stream assignment
-    p->op_stream.assign(desc->n_ops, 0);
-    p->op_wait_level.assign(desc->n_ops, -1);
-    auto level_of = [&](int tensor) { for (int l = 0; l < desc->n_levels; ++l) if (desc->level_tensor[l] == tensor) return l; return -1; };
-    for (int i = 0; i < desc->n_ops; ++i) {
-        const dn_op_desc& o = p->ops[i];
-        if (o.head) p->op_stream[i] = o.head;
-        else
-            for (int j = 0; j < desc->n_ops; ++j)
-                if (p->ops[j].head && p->ops[j].in == o.out && level_of(o.out) < 0) p->op_stream[i] = p->ops[j].head;
-    }
-    for (int i = 0; i < desc->n_ops; ++i) {
-        const dn_op_desc& o = p->ops[i];
-        if (p->op_stream[i]) p->op_wait_level[i] = level_of(o.in);
-    }
-    {
-        const bool enabled = getenv("DN_HEAD_GROUPS") ? atoi(getenv("DN_HEAD_GROUPS")) != 0 : true;
-        int first = -1, last_main = -1;
-        for (int i = 0; i < desc->n_ops; ++i) {
-            if (p->op_stream[i]) { if (first < 0) first = i; }
-            else last_main = i;
-        }
-        bool ok = enabled && first > last_main && first >= 0;
-        int kinds = 0;
-        for (int i = first; ok && i < desc->n_ops; ++i) {
-            const dn_op_desc& o = p->ops[i];
-            if (o.type == DN_OP_DW) {
-                if (o.pool >= 0 || o.k != p->ops[first].k || o.stride != p->ops[first].stride || p->ops[first].type != DN_OP_DW) { ok = false; break; }
-                p->head_dw.push_back(i);
-            } else if ((o.type == DN_OP_PW || o.type == DN_OP_CONV) && o.head) {
-                kinds |= (o.type == DN_OP_PW) ? 1 : 2;
-                (o.head == 1 ? p->head_cls : p->head_reg).push_back(i);
-            } else ok = false;
-        }
-        if (ok && (kinds == 3 || p->head_dw.size() > 12 || p->head_cls.size() > 8 || p->head_reg.size() > 8 || p->head_cls.empty())) ok = false;
-        if (ok) p->head_first = first;
-        else { p->head_dw.clear(); p->head_cls.clear(); p->head_reg.clear(); }
-    }
-    // ---- tail run: the longest suffix of the backbone (ops before the heads) that is a linear chain of tiny layers
-    if ((getenv("DN_TAIL") ? atoi(getenv("DN_TAIL")) : 1) != 0) {
-        const int end = p->head_first >= 0 ? p->head_first : desc->n_ops;
-        int first = end;
-        while (first > 0) {
-            const int i = first - 1;
-            const dn_op_desc& o = p->ops[i];
-            const dn_tensor_desc& ti = p->tensors[o.in];
-            const dn_tensor_desc& to = p->tensors[o.out];
-            bool fused = p->fused_len[i] > 0;
-            for (int q = 1; q <= 2 && i - q >= 0; ++q) fused |= p->fused_len[i - q] > q;
-            if (fused || ti.kind != DN_T_ACT || !tail_op_supported(o, ti.h, ti.w, to.h, to.w)) break;
-            if (first < end && p->ops[first].in != o.out) break;         // must feed the next op of the run
-            --first;
-        }
-        if (end - first > TAIL_MAX_OPS) first = end - TAIL_MAX_OPS;
-        if (end - first >= 2) {
-            p->tail_first = first;
-            p->tail_end = end;
-            p->tail_materialise.assign(end - first, 0);
-            for (int i = first; i < end; ++i) {
-                const int t = p->ops[i].out;
-                bool outside = false;
-                for (int l = 0; l < desc->n_levels; ++l) outside |= desc->level_tensor[l] == t;
-                for (int j = 0; j < desc->n_ops; ++j) {
-                    if (j >= first && j < end) continue;
-                    const dn_op_desc& u = p->ops[j];
-                    outside |= (u.in == t || u.residual == t || u.se == t);
-                }
-                p->tail_materialise[i - first] = outside ? 1 : 0;
-            }
-        }
-    }
+    plan_launches(p, weights);
     p->graph_mode = dn_knob("DN_GRAPH", 1) != 0;      // DN_GRAPH=0: plain launches (diagnostics)
-    p->xcd = getenv("DN_XCD") ? atoi(getenv("DN_XCD")) != 0 : true;
+    p->xcd = dn_knob("DN_XCD", 1) != 0;
     p->chain_graphs = dn_knob("DN_CHAIN_GRAPHS", -1);      // -1: auto (forward_impl)
     p->ws_reuse = dn_knob("DN_WS_REUSE", 1) != 0;
-    p->split = getenv("DN_SPLIT") ? atoi(getenv("DN_SPLIT")) : 2;
-    if (p->split < 1) p->split = 1;
-    if (p->split > 4) p->split = 4;
+    p->split = std::max(1, std::min(4, dn_knob("DN_SPLIT", 2)));
     // anchor offsets per level
     int acc = 0;
     for (int l = 0; l < desc->n_levels; ++l) {
@@ -694,11 +705,439 @@ static const Layout& get_sub_layout(dn_plan* p, int n, int S, int k) {
 // ---------------------------------------------------------------------------------------------------------
 // the launch sequence
 // ---------------------------------------------------------------------------------------------------------
+// what the launches of one chain address: its workspace view, its images and the weights arena
+struct Ctx {
+    const dn_plan* p;
+    const Layout& L;
+    unsigned char* ws;
+    int n, xq;              // images of this (sub-)batch; images per XCD group, 0: plain mapping
+    template <class T> T* t(int tid) const { return reinterpret_cast<T*>(ws + L.toff[tid]); }
+    template <class T> const T* w(long off) const { return reinterpret_cast<const T*>(p->weights_dev + off); }
+};
+
+// Profiling event segments of one chain: segment i (events[ev0 + i] -> [ev0 + i + 1]) belongs to op i. A launch over ops
+// [first, first + len) opens segment `first`, closes one segment after each of its kernel launches and pads up to first + len, so
+// that it records exactly len events; prof_kernel / prof_owner map each op to the kernel it took part in and the segment holding it.
+struct Segments {
+    dn_plan* p;
+    hipStream_t s;
+    int ev0;
+    bool rec;
+    int seg = 0, end = 0;
+    void record(int q) const { if (rec) (void)hipEventRecord(p->events[ev0 + q], s); }
+    void begin(const Launch& l) { seg = l.first; end = l.first + l.len; record(seg); }
+    // after a kernel launch: note() each of its ops (it took the last noted kernel), then close() the segment
+    void note(int q) const { if (rec) { p->prof_kernel[q] = dn_last_kernel(); p->prof_owner[q] = seg; } }
+    void close() { if (++seg < end) record(seg); }
+    template <class Ops> void launched(const Ops& ops) { for (int q : ops) note(q); close(); }
+    void finish() const { for (int q = seg + 1; q < end; ++q) record(q); }
+};
+
+// what the fused head launch leaves to the post-process when it ran softmax + decode in its epilogue (headfuse.hip, SM)
+struct HeadEpilogue {
+    bool scores_ready = false;
+    HistRows rows;
+    int small_first = -1;
+};
+
+// a head conv writes fp32 into the logits / regression array at its level's anchor offset, every other conv its fp16 tensor
+template <class A> static void set_output(const Ctx& c, const dn_op_desc& o, A& a) {
+    if (o.head) {
+        const int cols = (o.head == 1) ? c.p->d.num_classes : 4;
+        a.out = c.ws + (o.head == 1 ? c.L.logits_off : c.L.reg_off);
+        a.out_fp32 = 1;
+        a.out_img_stride = (long)c.p->d.num_anchors * cols;
+        a.out_base = (long)c.p->level_off[o.level] * cols;
+    } else {
+        a.out = c.t<void>(o.out);
+        a.out_fp32 = 0; a.out_img_stride = 0; a.out_base = 0;
+    }
+}
+
+static PwArgs make_pw(const Ctx& c, const dn_op_desc& o) {
+    const dn_tensor_desc& ti = c.p->tensors[o.in];
+    PwArgs a;
+    a.x = c.t<const half_t>(o.in);
+    a.w = c.w<half_t>(o.w_off);
+    a.wfrag = (o.type == DN_OP_PW && o.w2_off >= 0) ? c.w<half_t>(o.w2_off) : nullptr;
+    a.bias = c.w<float>(o.b_off);
+    a.residual = o.residual >= 0 ? c.t<const half_t>(o.residual) : nullptr;
+    a.se = o.se >= 0 ? c.t<const float>(o.se) : nullptr;
+    a.hw = ti.h * ti.w;
+    a.m = c.n * a.hw;
+    a.cin = o.cin; a.cout = o.cout; a.act = o.act;
+    a.xq = c.xq;
+    set_output(c, o, a);
+    return a;
+}
+
+static DwArgs make_dw(const Ctx& c, const dn_op_desc& o) {
+    const dn_tensor_desc& ti = c.p->tensors[o.in];
+    const dn_tensor_desc& to = c.p->tensors[o.out];
+    DwArgs a;
+    a.x = c.t<const half_t>(o.in);
+    a.w = c.w<half_t>(o.w_off);
+    a.bias = c.w<float>(o.b_off);
+    a.out = c.t<half_t>(o.out);
+    a.n = c.n; a.h = ti.h; a.w_ = ti.w; a.c = o.cin; a.k = o.k; a.stride = o.stride; a.pad = o.pad; a.act = o.act;
+    a.ho = to.h; a.wo = to.w;
+    a.pool = o.pool >= 0 ? c.t<float>(o.pool) : nullptr;
+    a.pool_rows = o.pool >= 0 ? c.p->pool_blocks[o.pool] : 0;
+    a.xq = c.xq;
+    return a;
+}
+
+static ConvArgs make_conv(const Ctx& c, const dn_op_desc& o) {
+    const dn_tensor_desc& ti = c.p->tensors[o.in];
+    const dn_tensor_desc& to = c.p->tensors[o.out];
+    ConvArgs a;
+    a.x = c.t<const half_t>(o.in);
+    a.w = c.w<half_t>(o.w_off);
+    a.bias = c.w<float>(o.b_off);
+    a.zeros = c.w<half_t>((long)c.p->zeros_off);
+    a.n = c.n; a.h = ti.h; a.w_ = ti.w; a.cin = o.cin; a.cout = o.cout; a.k = o.k; a.stride = o.stride;
+    a.pad = o.pad; a.dil = o.dil; a.act = o.act; a.ho = to.h; a.wo = to.w;
+    a.xq = c.xq;
+    set_output(c, o, a);
+    return a;
+}
+
+static int run_single(const Ctx& c, const Launch& l, const float* net_in, hipStream_t s) {
+    const dn_plan* p = c.p;
+    const dn_op_desc& o = p->ops[l.first];
+    const dn_tensor_desc& ti = p->tensors[o.in];
+    const dn_tensor_desc& to = p->tensors[o.out];
+    switch (o.type) {
+        case DN_OP_STEM: {
+            StemArgs a;
+            a.img = net_in;
+            a.w = c.w<float>(o.w_off);
+            a.bias = c.w<float>(o.b_off);
+            a.out = c.t<half_t>(o.out);
+            a.n = c.n; a.h = ti.h; a.w_ = ti.w; a.cout = o.cout; a.k = o.k; a.stride = o.stride; a.pad = o.pad; a.act = o.act;
+            a.ho = to.h; a.wo = to.w;
+            for (int q = 0; q < 3; ++q) { a.mean[q] = p->d.mean[q]; a.inv_std[q] = 1.0f / p->d.std[q]; }
+            a.xq = c.xq;
+            a.split_ok = l.stem_split ? 1 : 0;
+            a.w_scale = std::ldexp(1.0f, l.stem_scale_log2);
+            a.w_unscale = std::ldexp(1.0f, -l.stem_scale_log2);
+            if (p->n_se_in_dw > 0) { a.zero_u32 = reinterpret_cast<unsigned*>(c.ws + c.L.secnt_off); a.zero_count = p->n_se_in_dw * c.n; }
+            return launch_stem(a, s);
+        }
+        case DN_OP_PW: {
+            PwArgs a = make_pw(c, o);
+            if (l.se >= 0) {
+                // the squeeze-excitation FCs run in this projection's prologue: hand over the pooled partial sums and the FC weights
+                const dn_op_desc& so = p->ops[l.se];
+                a.se = nullptr;
+                a.sef_part = c.t<const float>(so.in);
+                a.sef_nblk = p->pool_blocks[so.in];
+                a.sef_sq = so.squeeze;
+                a.sef_inv = 1.0f / (float)so.pool_pixels;
+                a.sef_w1t = c.w<half_t>(so.w_off); a.sef_b1 = c.w<float>(so.b_off);
+                a.sef_w2t = c.w<half_t>(so.w2_off); a.sef_b2 = c.w<float>(so.b2_off);
+            }
+            return launch_pointwise(a, s);
+        }
+        case DN_OP_DW: {
+            DwArgs a = make_dw(c, o);
+            if (l.se >= 0) {
+                const dn_op_desc& so = p->ops[l.se];
+                a.se_w1t = c.w<half_t>(so.w_off); a.se_b1 = c.w<float>(so.b_off);
+                a.se_w2t = c.w<half_t>(so.w2_off); a.se_b2 = c.w<float>(so.b2_off);
+                a.se_scale = c.t<float>(so.out);
+                a.se_counter = reinterpret_cast<unsigned*>(c.ws + c.L.secnt_off) + (size_t)l.se_slot * c.n;
+                a.se_sq = so.squeeze;
+                a.se_inv = 1.0f / (float)so.pool_pixels;
+            }
+            return launch_depthwise(a, s);
+        }
+        case DN_OP_SE:
+            if (l.se_host >= 0) {
+                dn_note_kernel(p->ops[l.se_host].type == DN_OP_PW ? "(se folded into the projection)" : "(se in the tail of the depthwise launch)");
+                return DN_OK;
+            }
+            return launch_se_fc(c.t<const float>(o.in), p->pool_blocks[o.in], c.w<unsigned char>(o.w_off), c.w<float>(o.b_off),
+                                c.w<unsigned char>(o.w2_off), c.w<float>(o.b2_off), c.t<float>(o.out), c.n, o.cin, o.squeeze,
+                                o.pool_pixels, s, c.xq);
+        case DN_OP_CONV:
+            return launch_conv(make_conv(c, o), s);
+        case DN_OP_MAXPOOL:
+            return launch_maxpool(c.t<const half_t>(o.in), c.t<half_t>(o.out), c.n, ti.h, ti.w, ti.c, o.k, o.stride, o.pad, to.h, to.w, s);
+        case DN_OP_L2NORM:
+            return launch_l2norm(c.t<const half_t>(o.in), c.w<float>(o.w_off), c.t<half_t>(o.out), (long)c.n * ti.h * ti.w, ti.c, s);
+    }
+    return DN_OK;
+}
+
+static int run_expdw(const Ctx& c, const Launch& l, hipStream_t s) {
+    const dn_plan* p = c.p;
+    const dn_op_desc* e = l.has_expand ? &p->ops[l.first] : nullptr;
+    const dn_op_desc& dwo = p->ops[l.first + (l.has_expand ? 1 : 0)];
+    const dn_op_desc* pj = l.has_project ? &p->ops[l.first + l.len - 1] : nullptr;
+    const dn_tensor_desc& tin = p->tensors[p->ops[l.first].in];
+    const dn_tensor_desc& tdo = p->tensors[dwo.out];
+    ExpDwArgs a{};
+    a.x = c.t<const half_t>(p->ops[l.first].in);
+    a.out = c.t<half_t>(pj ? pj->out : dwo.out);
+    a.pool = dwo.pool >= 0 ? c.t<float>(dwo.pool) : nullptr;
+    if (e) { a.w1 = c.w<half_t>(e->w_off); a.b1 = c.w<float>(e->b_off); a.act1 = e->act; }
+    a.wd = c.w<half_t>(dwo.w_off); a.bd = c.w<float>(dwo.b_off); a.act2 = dwo.act;
+    if (pj) { a.w3 = c.w<half_t>(pj->w_off); a.b3 = c.w<float>(pj->b_off); }
+    a.n = c.n; a.H = tin.h; a.W = tin.w; a.Ho = tdo.h; a.Wo = tdo.w;
+    a.cin = tin.c; a.cexp = dwo.cin; a.cout = pj ? pj->cout : dwo.cin;
+    a.k = dwo.k; a.stride = dwo.stride; a.pad = dwo.pad;
+    a.has_res = (pj && pj->residual >= 0) ? 1 : 0;
+    a.xq = c.xq;
+    return launch_expdw(a, s);
+}
+
+static int run_pw_dw(const Ctx& c, const Launch& l, hipStream_t s) {
+    PwArgs pa = make_pw(c, c.p->ops[l.first + 1]);
+    const DwArgs da = make_dw(c, c.p->ops[l.first]);
+    pa.x = da.x;                                    // (the depthwise output is not materialised)
+    if (pa.residual) pa.residual = da.x;
+    return launch_pw_dw_direct(pa, da, s);
+}
+
+static int run_conv_pool(const Ctx& c, const Launch& l, hipStream_t s) {
+    const dn_op_desc& o = c.p->ops[l.first];
+    PwArgs pa = conv_to_pw(make_conv(c, o));
+    if (c.L.toff[o.out] == (size_t)-1) pa.out = nullptr;      // (materialised only when something else reads the full-resolution map)
+    pa.pool_out = c.t<half_t>(c.p->ops[l.first + 1].out);
+    return launch_conv_pool(pa, s);
+}
+
+static int run_tail(const Ctx& c, const Launch& l, hipStream_t s) {
+    const dn_plan* p = c.p;
+    TailArgs ta{};
+    ta.count = l.len;
+    ta.weights = c.w<half_t>(0);
+    const dn_op_desc& o0 = p->ops[l.first];
+    ta.in0 = c.t<const half_t>(o0.in);
+    ta.in0_stride = (long)(c.L.tbytes[o0.in] / (size_t)c.L.n / 2);
+    ta.xq = c.xq;
+    for (int q = 0; q < ta.count; ++q) {
+        const dn_op_desc& oq = p->ops[l.first + q];
+        const dn_tensor_desc& tq = p->tensors[oq.in];
+        const dn_tensor_desc& uq = p->tensors[oq.out];
+        TailOp& t = ta.op[q];
+        t.type = oq.type; t.cin = oq.cin; t.cout = oq.type == DN_OP_DW ? oq.cin : oq.cout; t.k = oq.k; t.stride = oq.stride; t.pad = oq.pad;
+        t.hin = tq.h; t.win = tq.w; t.hout = uq.h; t.wout = uq.w; t.act = oq.act;
+        t.w_off = (long)((oq.type == DN_OP_PW ? oq.w2_off : oq.w_off) / 2); t.b_off = (long)oq.b_off;
+        t.out = l.materialise[q] ? c.t<half_t>(oq.out) : nullptr;
+        t.out_stride = (long)(c.L.tbytes[oq.out] / (size_t)c.L.n / 2);
+    }
+    return launch_tail(ta, c.n, s);
+}
+
+// SSDLite heads (depthwise 3x3 -> 1x1, class and box head per level): the levels whose class and box head are both (depthwise 3x3
+// stride 1 -> 1x1) chains on the level's feature map, as HeadFuseLevels of ONE launch (headfuse.hip) -- no depthwise output in HBM,
+// no second launch. members: the four ops (class dw, box dw, class conv, box conv) of every level that joins.
+static int fused_head_levels(const Ctx& c, const Launch& l, HeadFuseLevel* fl, std::vector<int>& members) {
+    const dn_plan* p = c.p;
+    int nl = 0;
+    for (size_t q = 0; q < l.head_cls.size() && nl < 8; ++q) {
+        const dn_op_desc& oc = p->ops[l.head_cls[q]];
+        int qr = -1;
+        for (int u : l.head_reg) if (p->ops[u].level == oc.level) qr = u;
+        if (qr < 0 || oc.type != DN_OP_PW || p->ops[qr].type != DN_OP_PW) continue;
+        const dn_op_desc& orr = p->ops[qr];
+        int dc = -1, dr = -1;
+        for (int u : l.head_dw) { if (p->ops[u].out == oc.in) dc = u; if (p->ops[u].out == orr.in) dr = u; }
+        if (dc < 0 || dr < 0) continue;
+        const dn_op_desc &odc = p->ops[dc], &odr = p->ops[dr];
+        if (odc.in != odr.in || odc.k != 3 || odr.k != 3 || odc.stride != 1 || odr.stride != 1 || odc.pad != 1 || odr.pad != 1 || odc.dil != 1 ||
+            odr.dil != 1 || odc.act != odr.act || odc.cin != odr.cin || oc.cin != odc.cin || orr.cin != odc.cin || oc.act != DN_ACT_NONE ||
+            orr.act != DN_ACT_NONE || oc.se >= 0 || orr.se >= 0 || oc.residual >= 0 || orr.residual >= 0 || oc.w2_off < 0 || orr.w2_off < 0 ||
+            odc.pool >= 0 || odr.pool >= 0) continue;
+        const dn_tensor_desc& ti = p->tensors[odc.in];
+        HeadFuseLevel& f = fl[nl];
+        f.x = c.t<const half_t>(odc.in);
+        const dn_op_desc* op[2] = {&oc, &orr};
+        for (int hsel = 0; hsel < 2; ++hsel) {
+            const PwArgs pa = make_pw(c, *op[hsel]);
+            f.wf[hsel] = pa.wfrag; f.bias[hsel] = pa.bias;
+            f.out[hsel] = reinterpret_cast<float*>(pa.out); f.out_img_stride[hsel] = pa.out_img_stride; f.out_base[hsel] = pa.out_base;
+            f.nc[hsel] = pa.cout;
+        }
+        f.wdg = odc.w2_off >= 0 ? c.w<half_t>(odc.w2_off) : nullptr;
+        f.wslot = odc.b2_off >= 0 ? c.w<unsigned char>(odc.b2_off) : nullptr;
+        f.n = c.n; f.H = ti.h; f.W = ti.w; f.C = odc.cin; f.act = odc.act;
+        if (!head_fused_level_supported(f)) continue;
+        // DN_HEAD_FUSE_MINHW: levels with fewer pixels per image stay on the grouped launches. The fused workgroups take 512 residency
+        // slots (2 per CU); at batch 64 levels 0 - 1 are 504 of them, every further workgroup starts a second round of the whole launch
+        if (ti.h * ti.w < dn_knob("DN_HEAD_FUSE_MINHW", 0)) continue;
+        if (nl > 0 && (dn_cdiv(f.nc[0], 32) + 4) / 4 != (dn_cdiv(fl[0].nc[0], 32) + 4) / 4) continue;      // (one instantiation per launch: channel tiles per wave)
+        ++nl;
+        members.push_back(dc); members.push_back(dr); members.push_back(l.head_cls[q]); members.push_back(qr);
+    }
+    return nl;
+}
+
+// softmax + decode + histogram rows in the epilogue of the fused head launch (DN_HEAD_SOFTMAX, default 1) when EVERY level's heads
+// are in it and the post-process follows (dn_forward_heads wants the logits themselves). False: the launch writes logits only.
+static bool head_softmax_epilogue(const Ctx& c, HeadFuseLevel* fl, int nl, const std::vector<int>& members, HeadPost& hp, HeadEpilogue& ep) {
+    const dn_plan* p = c.p;
+    const dn_model_desc& d = p->d;
+    // From 32 images per chain up (DN_HEAD_SOFTMAX_MINN): below that the launch is far from filling the chip and the epilogue is pure
+    // latency on the chain (batch 32 as two chains of 16: 0.630 -> 0.648 ms one forward at a time; from 32 per chain up it gains).
+    if (dn_knob("DN_HEAD_SOFTMAX", 1) == 0 || c.n < dn_knob("DN_HEAD_SOFTMAX_MINN", 32)) return false;
+    const PostBuffers pb = post_buffers(c.ws + c.L.post_off, c.n, d.num_anchors, d.num_classes, d.topk_candidates);
+    int clamped = 0;
+    post_hist_range(d.score_thresh, &hp.hb0, &hp.nb, &clamped);
+    hp.scoresT = pb.scoresT; hp.boxes = pb.boxes; hp.hrows = pb.phist; hp.anchors = p->anchors_dev;
+    hp.A = d.num_anchors; hp.K = d.num_classes;
+    hp.img_w = (float)d.image_w; hp.img_h = (float)d.image_h; hp.score_thr = d.score_thresh;
+    // the levels with >= 32 pixels per image take the epilogue; they must be a prefix of the anchor axis (the rest -- anchors
+    // [small_first, A) -- gets its softmax in the cut-off launch, from the logits this launch writes for them)
+    HistRows hr;
+    int rows = 0, nsm = 0;
+    bool prefix = true;
+    for (int q = 0; q < nl; ++q) {
+        const int level = p->ops[members[4 * q + 2]].level;
+        fl[q].aoff = p->level_off[level];
+        fl[q].aloc = fl[q].nc[0] / d.num_classes;
+        fl[q].sm = fl[q].H * fl[q].W >= std::max(32, dn_knob("DN_HEAD_SM_MINHW", 32)) ? 1 : 0;
+        if (fl[q].sm) {
+            prefix = prefix && nsm == q && (q == 0 ? fl[q].aoff == 0 : fl[q].aoff == fl[q - 1].aoff + fl[q - 1].H * fl[q - 1].W * fl[q - 1].aloc);
+            fl[q].sbase = rows;
+            hr.hw[nsm] = fl[q].H * fl[q].W; hr.sbase[nsm] = rows; hr.grouped[nsm] = head_fused_grouped(c.xq, hr.hw[nsm]) ? 1 : 0;
+            rows += hist_rows_slots(hr.hw[nsm]);
+            ++nsm;
+        }
+    }
+    hr.levels = nsm;
+    hr.rows_per_image = rows;
+    // the epilogue levels must be pyramid levels 0 .. nsm - 1: everything behind them -- small levels of this launch and levels that did
+    // not join it (the V2 model's last level is a plain 1x1 conv on the grouped launches) -- stays in logit form
+    for (int q = 0; q < nsm; ++q) prefix = prefix && p->ops[members[4 * q + 2]].level == q;
+    // (the softmax tiles of those levels put their histogram rows behind these: the row stride of an image covers both)
+    const int sfirst = nsm < d.n_levels ? p->level_off[nsm] : d.num_anchors;
+    hp.rows_per_image = rows + dn_cdiv(d.num_anchors - sfirst, 64);
+    if (!(prefix && nsm > 0 && hp.rows_per_image <= pb.tiles && head_fused_post_supported(fl, nl, hp))) return false;
+    ep = HeadEpilogue{true, hr, sfirst};
+    return true;
+}
+
+// the grouped head launches: the depthwise group, then the 1x1 / dense group(s)
+static int run_head_groups(const Ctx& c, const std::vector<int>& h_dw, const std::vector<int>& h_cls, const std::vector<int>& h_reg,
+                           hipStream_t s, Segments& sg) {
+    const dn_plan* p = c.p;
+    int rc = DN_OK;
+    if (!h_dw.empty()) {
+        DwArgs arr[12];
+        for (size_t q = 0; q < h_dw.size(); ++q) arr[q] = make_dw(c, p->ops[h_dw[q]]);
+        rc = launch_depthwise_group(arr, (int)h_dw.size(), s);
+        if (rc != DN_OK) return rc;
+        sg.launched(h_dw);
+    }
+    // box and class heads of all levels in ONE launch when they fit (a dependent launch costs ~4.5 us even when empty, and
+    // the narrow box heads then share the class heads' tile instead of running as a launch of their own)
+    const bool merge_heads = dn_knob("DN_HEAD_MERGE", 1) != 0;
+    // (dense-conv heads leave in a narrow and a wide launch of at most 12 problems each, so 7 levels x 2 heads still go together --
+    // the box heads of the large levels must meet their class heads to ride in their tiles: 0.45 ms per 16 images on ssd512)
+    const bool conv_heads = !h_reg.empty() && p->ops[h_reg[0]].type == DN_OP_CONV;
+    const bool one = merge_heads && !h_reg.empty() && !h_cls.empty() && p->ops[h_reg[0]].type == p->ops[h_cls[0]].type &&
+                     (h_reg.size() + h_cls.size() <= 12 || (conv_heads && h_reg.size() <= 12 && h_cls.size() <= 12));
+    for (int kind = 0; kind < 2; ++kind) {
+        std::vector<int> lst = kind ? h_cls : h_reg;
+        if (one) {
+            if (kind == 1) break;
+            lst.insert(lst.end(), h_cls.begin(), h_cls.end());
+        }
+        if (lst.empty()) continue;
+        std::vector<PwArgs> arr(lst.size());
+        const bool conv = p->ops[lst[0]].type == DN_OP_CONV;
+        int cnt = 0;
+        std::vector<int> grouped;
+        std::set<int> taken;
+        // wide heads first, so that a box head that rides along is known before the groups are formed
+        std::stable_sort(lst.begin(), lst.end(), [&](int x, int y) { return p->ops[x].cout > p->ops[y].cout; });
+        for (size_t q = 0; q < lst.size(); ++q) {
+            PwArgs pa = conv ? conv_to_pw(make_conv(c, p->ops[lst[q]])) : make_pw(c, p->ops[lst[q]]);
+            if (conv && taken.count(lst[q])) continue;          // rides in another head's launch
+            if (conv && conv_head_big_supported(pa)) {
+                // the wide dense heads of the large levels: MFMA-bound, each on the run-staged 256x256 tile. The box head of the
+                // same level (same input, 16 / 24 channels) fits in the idle part of its last channel tile.
+                int rider = -1;
+                for (size_t u = 0; u < lst.size() && rider < 0; ++u) {
+                    const dn_op_desc &ou = p->ops[lst[u]], &oq = p->ops[lst[q]];
+                    if (u != q && !taken.count(lst[u]) && ou.in == oq.in && ou.type == oq.type && ou.k == oq.k && ou.stride == oq.stride &&
+                        ou.pad == oq.pad && ou.dil == oq.dil && ou.act == oq.act && ou.cout < oq.cout &&
+                        dn_cdiv(oq.cout + ou.cout, 256) == dn_cdiv(oq.cout, 256))
+                        rider = (int)u;
+                }
+                if (rider >= 0) {
+                    // the tile is chosen from cout + cout_b: the rider joins only if the launch still has a tile WITH it (21 classes x 6 anchors =
+                    // 126 + 24 channels cross a 128-channel tile boundary and fail the narrow-tile test the class head passed alone)
+                    const PwArgs pb = conv_to_pw(make_conv(c, p->ops[lst[rider]]));
+                    PwArgs with = pa;
+                    with.w_b = pb.w; with.bias_b = pb.bias; with.out_b = pb.out; with.cout_b = pb.cout;
+                    with.out_b_img_stride = pb.out_img_stride; with.out_b_base = pb.out_base;
+                    if (conv_head_big_supported(with)) { pa = with; taken.insert(lst[rider]); }
+                    else rider = -1;
+                }
+                rc = launch_conv_head_big(pa, s);
+                if (rc != DN_OK) return rc;
+                sg.note(lst[q]);
+                if (rider >= 0) sg.note(lst[rider]);
+                sg.close();
+                continue;
+            }
+            arr[cnt++] = pa;
+            grouped.push_back(lst[q]);
+        }
+        if (cnt == 0) continue;
+        // once the wide heads have left, the narrow box heads (16 / 24 channels) would pay the wide tile of the remaining
+        // class heads: dense-conv groups are split into a narrow and a wide launch
+        const bool split_narrow = conv && (cnt < (int)lst.size() || cnt > 12);
+        for (int pass = 0; pass < (split_narrow ? 2 : 1); ++pass) {
+            PwArgs sub[12];
+            std::vector<int> ids;
+            int nsub = 0;
+            for (int q = 0; q < cnt; ++q) {
+                const bool narrow = arr[q].cout <= 32;
+                if (split_narrow && narrow != (pass == 0)) continue;
+                DN_REQUIRE(nsub < 12, "head group: more than 12 problems in one launch");
+                sub[nsub++] = arr[q];
+                ids.push_back(grouped[q]);
+            }
+            if (nsub == 0) continue;
+            rc = launch_pointwise_group(sub, nsub, conv, s);
+            if (rc != DN_OK) return rc;
+            sg.launched(ids);
+        }
+    }
+    return DN_OK;
+}
+
+// the HEADS launch group: the fused head launch (DN_HEAD_FUSE=0 keeps the grouped launches: the reference path of the bit-identity
+// test), then the grouped launches for what did not join it (the V2 model's last level is a plain 1x1 conv). Decided per enqueue:
+// the choice depends on the chain's batch size and on knobs read at every launch.
+static int run_heads(const Ctx& c, const Launch& l, bool heads_only, hipStream_t s, Segments& sg, HeadEpilogue& ep) {
+    std::vector<int> h_dw = l.head_dw, h_cls = l.head_cls, h_reg = l.head_reg;
+    if (dn_knob("DN_HEAD_FUSE", 1) != 0 && !h_dw.empty() && !h_cls.empty() && !h_reg.empty()) {
+        HeadFuseLevel fl[8];
+        std::vector<int> members;
+        const int nl = fused_head_levels(c, l, fl, members);
+        if (nl > 0) {
+            HeadPost hp;
+            const bool with_post = !heads_only && head_softmax_epilogue(c, fl, nl, members, hp, ep);
+            const int rc = launch_head_fused(fl, nl, c.xq, s, with_post ? &hp : nullptr);
+            if (rc != DN_OK) return rc;
+            sg.launched(members);
+            auto joined = [&](int q) { return std::find(members.begin(), members.end(), q) != members.end(); };
+            for (std::vector<int>* v : {&h_dw, &h_cls, &h_reg}) v->erase(std::remove_if(v->begin(), v->end(), joined), v->end());
+        }
+    }
+    return run_head_groups(c, h_dw, h_cls, h_reg, s, sg);
+}
+
 static int enqueue(dn_plan* p, const float* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,
                    int32_t* counts, unsigned char* ws, const Layout& L, bool heads_only, hipStream_t s, bool record,
-                   float* packed, int ev0 = 0, int chain = 0) {
+                   float* packed, int ev0 = 0) {
     const dn_model_desc& d = p->d;
-    auto tptr = [&](int tid) -> void* { return ws + L.toff[tid]; };
     const float* net_in = images;
     const bool resize = (h != d.image_h || w != d.image_w);
     float* scale_xy = nullptr;
@@ -718,482 +1157,48 @@ static int enqueue(dn_plan* p, const float* images, int n, int h, int w, float* 
         if (rc) return rc;
         net_in = rz;
     }
-    float* logits = reinterpret_cast<float*>(ws + L.logits_off);
-    float* reg = reinterpret_cast<float*>(ws + L.reg_off);
-    const unsigned char* const Wb = p->weights_dev;
-    const int xq = (p->xcd && n >= 8) ? (n + 7) / 8 : 0;        // images per XCD group of this (sub-)batch, 0: plain mapping
-    auto make_pw = [&](const dn_op_desc& o) {
-        const dn_tensor_desc& ti = p->tensors[o.in];
-        PwArgs a;
-        a.x = reinterpret_cast<const half_t*>(tptr(o.in));
-        a.w = reinterpret_cast<const half_t*>(Wb + o.w_off);
-        a.wfrag = (o.type == DN_OP_PW && o.w2_off >= 0) ? reinterpret_cast<const half_t*>(Wb + o.w2_off) : nullptr;
-        a.bias = reinterpret_cast<const float*>(Wb + o.b_off);
-        a.residual = o.residual >= 0 ? reinterpret_cast<const half_t*>(tptr(o.residual)) : nullptr;
-        a.se = o.se >= 0 ? reinterpret_cast<const float*>(tptr(o.se)) : nullptr;
-        a.hw = ti.h * ti.w;
-        a.m = n * a.hw;
-        a.cin = o.cin; a.cout = o.cout; a.act = o.act;
-        a.xq = xq;
-        const int oi = (int)(&o - p->ops.data());
-        if (oi >= 0 && oi < (int)p->ops.size() && p->se_fold[oi] >= 0) {
-            // the squeeze-excitation FCs run in this projection's prologue: hand over the pooled partial sums and the FC weights
-            const dn_op_desc& so = p->ops[p->se_fold[oi]];
-            a.se = nullptr;
-            a.sef_part = reinterpret_cast<const float*>(tptr(so.in));
-            a.sef_nblk = p->pool_blocks[so.in];
-            a.sef_sq = so.squeeze;
-            a.sef_inv = 1.0f / (float)so.pool_pixels;
-            a.sef_w1t = reinterpret_cast<const half_t*>(Wb + so.w_off); a.sef_b1 = reinterpret_cast<const float*>(Wb + so.b_off);
-            a.sef_w2t = reinterpret_cast<const half_t*>(Wb + so.w2_off); a.sef_b2 = reinterpret_cast<const float*>(Wb + so.b2_off);
-        }
-        if (o.head) {
-            const int cols = (o.head == 1) ? d.num_classes : 4;
-            a.out = (o.head == 1) ? (void*)logits : (void*)reg;
-            a.out_fp32 = 1;
-            a.out_img_stride = (long)d.num_anchors * cols;
-            a.out_base = (long)p->level_off[o.level] * cols;
-        } else {
-            a.out = tptr(o.out);
-            a.out_fp32 = 0; a.out_img_stride = 0; a.out_base = 0;
-        }
-        return a;
-    };
-    auto make_dw = [&](const dn_op_desc& o) {
-        const dn_tensor_desc& ti = p->tensors[o.in];
-        const dn_tensor_desc& to = p->tensors[o.out];
-        DwArgs a;
-        a.x = reinterpret_cast<const half_t*>(tptr(o.in));
-        a.w = reinterpret_cast<const half_t*>(Wb + o.w_off);
-        a.bias = reinterpret_cast<const float*>(Wb + o.b_off);
-        a.out = reinterpret_cast<half_t*>(tptr(o.out));
-        a.n = n; a.h = ti.h; a.w_ = ti.w; a.c = o.cin; a.k = o.k; a.stride = o.stride; a.pad = o.pad; a.act = o.act;
-        a.ho = to.h; a.wo = to.w;
-        a.pool = o.pool >= 0 ? reinterpret_cast<float*>(tptr(o.pool)) : nullptr;
-        a.pool_rows = o.pool >= 0 ? p->pool_blocks[o.pool] : 0;
-        a.xq = xq;
-        const int oi = (int)(&o - p->ops.data());
-        if (oi >= 0 && oi < (int)p->ops.size() && p->se_in_dw[oi] >= 0) {
-            const dn_op_desc& so = p->ops[p->se_in_dw[oi]];
-            a.se_w1t = reinterpret_cast<const half_t*>(Wb + so.w_off); a.se_b1 = reinterpret_cast<const float*>(Wb + so.b_off);
-            a.se_w2t = reinterpret_cast<const half_t*>(Wb + so.w2_off); a.se_b2 = reinterpret_cast<const float*>(Wb + so.b2_off);
-            a.se_scale = reinterpret_cast<float*>(tptr(so.out));
-            a.se_counter = reinterpret_cast<unsigned*>(ws + L.secnt_off) + (size_t)p->se_slot[oi] * n;
-            a.se_sq = so.squeeze;
-            a.se_inv = 1.0f / (float)so.pool_pixels;
-        }
-        return a;
-    };
-    auto make_conv = [&](const dn_op_desc& o) {
-        const dn_tensor_desc& ti = p->tensors[o.in];
-        const dn_tensor_desc& to = p->tensors[o.out];
-        ConvArgs a;
-        a.x = reinterpret_cast<const half_t*>(tptr(o.in));
-        a.w = reinterpret_cast<const half_t*>(Wb + o.w_off);
-        a.bias = reinterpret_cast<const float*>(Wb + o.b_off);
-        a.zeros = reinterpret_cast<const half_t*>(Wb + p->zeros_off);
-        a.n = n; a.h = ti.h; a.w_ = ti.w; a.cin = o.cin; a.cout = o.cout; a.k = o.k; a.stride = o.stride;
-        a.pad = o.pad; a.dil = o.dil; a.act = o.act; a.ho = to.h; a.wo = to.w;
-        a.xq = xq;
-        if (o.head) {
-            const int cols = (o.head == 1) ? d.num_classes : 4;
-            a.out = (o.head == 1) ? (void*)logits : (void*)reg;
-            a.out_fp32 = 1;
-            a.out_img_stride = (long)d.num_anchors * cols;
-            a.out_base = (long)p->level_off[o.level] * cols;
-        } else {
-            a.out = tptr(o.out);
-            a.out_fp32 = 0; a.out_img_stride = 0; a.out_base = 0;
-        }
-        return a;
-    };
-    int ev = ev0;
-    hipStream_t const main_stream = s;
-    // set by launch_heads when the fused head launch also ran softmax + decode (headfuse.hip, SM): the post-process starts at the cut-off
-    bool scores_ready = false;
-    HistRows fused_rows;
-    int small_first = -1;
-    // head launches of the pyramid levels [lv0, lv1): the depthwise group, then the 1x1 / dense group(s), on stream hs
-    auto launch_heads = [&](int lv0, int lv1, hipStream_t hs, bool rec, size_t& seg) -> int {
-        int rc = DN_OK;
-        auto hnote = [&](size_t op, size_t owner) {
-            if (!rec) return;
-            p->prof_kernel[op] = dn_last_kernel();
-            p->prof_owner[op] = (int)owner;
-        };
-        std::vector<int> h_dw, h_cls, h_reg;
-        for (int q : p->head_dw) if (p->op_wait_level[q] >= lv0 && p->op_wait_level[q] < lv1) h_dw.push_back(q);
-        for (int q : p->head_cls) if (p->ops[q].level >= lv0 && p->ops[q].level < lv1) h_cls.push_back(q);
-        for (int q : p->head_reg) if (p->ops[q].level >= lv0 && p->ops[q].level < lv1) h_reg.push_back(q);
-        // SSDLite heads (depthwise 3x3 -> 1x1, class and box head per level): ONE launch with the depthwise computed inside the 1x1 GEMM's
-        // operand staging (headfuse.hip) -- no depthwise output in HBM, no second launch. DN_HEAD_FUSE=0 keeps the two grouped launches
-        // (the reference path of the bit-identity test).
-        if (dn_knob("DN_HEAD_FUSE", 1) != 0 && !h_dw.empty() && !h_cls.empty() && !h_reg.empty()) {
-            HeadFuseLevel fl[8];
-            int nl = 0;
-            std::vector<int> members;
-            for (size_t q = 0; q < h_cls.size() && nl < 8; ++q) {
-                // a level joins when its class and box head are both (depthwise 3x3 stride 1 -> 1x1) chains on the level's feature map
-                const dn_op_desc& oc = p->ops[h_cls[q]];
-                int qr = -1;
-                for (int u : h_reg) if (p->ops[u].level == oc.level) qr = u;
-                if (qr < 0 || oc.type != DN_OP_PW || p->ops[qr].type != DN_OP_PW) continue;
-                const dn_op_desc& orr = p->ops[qr];
-                int dc = -1, dr = -1;
-                for (int u : h_dw) { if (p->ops[u].out == oc.in) dc = u; if (p->ops[u].out == orr.in) dr = u; }
-                if (dc < 0 || dr < 0) continue;
-                const dn_op_desc &odc = p->ops[dc], &odr = p->ops[dr];
-                if (odc.in != odr.in || odc.k != 3 || odr.k != 3 || odc.stride != 1 || odr.stride != 1 || odc.pad != 1 || odr.pad != 1 || odc.dil != 1 ||
-                    odr.dil != 1 || odc.act != odr.act || odc.cin != odr.cin || oc.cin != odc.cin || orr.cin != odc.cin || oc.act != DN_ACT_NONE ||
-                    orr.act != DN_ACT_NONE || oc.se >= 0 || orr.se >= 0 || oc.residual >= 0 || orr.residual >= 0 || oc.w2_off < 0 || orr.w2_off < 0 ||
-                    odc.pool >= 0 || odr.pool >= 0) continue;
-                const dn_tensor_desc& ti = p->tensors[odc.in];
-                HeadFuseLevel& f = fl[nl];
-                f.x = reinterpret_cast<const half_t*>(tptr(odc.in));
-                const dn_op_desc* op[2] = {&oc, &orr};
-                for (int hsel = 0; hsel < 2; ++hsel) {
-                    const PwArgs pa = make_pw(*op[hsel]);
-                    f.wf[hsel] = pa.wfrag; f.bias[hsel] = pa.bias;
-                    f.out[hsel] = reinterpret_cast<float*>(pa.out); f.out_img_stride[hsel] = pa.out_img_stride; f.out_base[hsel] = pa.out_base;
-                    f.nc[hsel] = pa.cout;
-                }
-                f.wdg = odc.w2_off >= 0 ? reinterpret_cast<const half_t*>(Wb + odc.w2_off) : nullptr;
-                f.wslot = odc.b2_off >= 0 ? Wb + odc.b2_off : nullptr;
-                f.n = n; f.H = ti.h; f.W = ti.w; f.C = odc.cin; f.act = odc.act;
-                if (!head_fused_level_supported(f)) continue;
-                // DN_HEAD_FUSE_MINHW: levels with fewer pixels per image stay on the grouped launches. The fused workgroups take 512 residency
-                // slots (2 per CU); at batch 64 levels 0 - 1 are 504 of them, every further workgroup starts a second round of the whole launch
-                if (ti.h * ti.w < dn_knob("DN_HEAD_FUSE_MINHW", 0)) continue;
-                if (nl > 0 && (dn_cdiv(f.nc[0], 32) + 4) / 4 != (dn_cdiv(fl[0].nc[0], 32) + 4) / 4) continue;      // (one instantiation per launch: channel tiles per wave)
-                ++nl;
-                members.push_back(dc); members.push_back(dr); members.push_back(h_cls[q]); members.push_back(qr);
-            }
-            if (nl > 0) {
-                // softmax + decode + histogram rows in the same launch (DN_HEAD_SOFTMAX, default 1) when EVERY level's heads are in it and the
-                // post-process follows (dn_forward_heads wants the logits themselves)
-                HeadPost hp;
-                bool with_post = false;
-                // From 32 images per chain up (DN_HEAD_SOFTMAX_MINN): below that the launch is far from filling the chip and the epilogue is pure
-                // latency on the chain (batch 32 as two chains of 16: 0.630 -> 0.648 ms one forward at a time; from 32 per chain up it gains).
-                if (!heads_only && dn_knob("DN_HEAD_SOFTMAX", 1) != 0 && n >= dn_knob("DN_HEAD_SOFTMAX_MINN", 32) && lv0 == 0 && lv1 >= d.n_levels) {
-                    const PostBuffers pb = post_buffers(ws + L.post_off, n, d.num_anchors, d.num_classes, d.topk_candidates);
-                    int clamped = 0;
-                    post_hist_range(d.score_thresh, &hp.hb0, &hp.nb, &clamped);
-                    hp.scoresT = pb.scoresT; hp.boxes = pb.boxes; hp.hrows = pb.phist; hp.anchors = p->anchors_dev;
-                    hp.A = d.num_anchors; hp.K = d.num_classes;
-                    hp.img_w = (float)d.image_w; hp.img_h = (float)d.image_h; hp.score_thr = d.score_thresh;
-                    // the levels with >= 32 pixels per image take the epilogue; they must be a prefix of the anchor axis (the rest -- anchors
-                    // [small_first, A) -- gets its softmax in the cut-off launch, from the logits this launch writes for them)
-                    HistRows hr;
-                    int rows = 0, nsm = 0;
-                    bool prefix = true;
-                    for (int q = 0; q < nl; ++q) {
-                        const int level = p->ops[members[4 * q + 2]].level;
-                        fl[q].aoff = p->level_off[level];
-                        fl[q].aloc = fl[q].nc[0] / d.num_classes;
-                        fl[q].sm = fl[q].H * fl[q].W >= std::max(32, dn_knob("DN_HEAD_SM_MINHW", 32)) ? 1 : 0;
-                        if (fl[q].sm) {
-                            prefix = prefix && nsm == q && (q == 0 ? fl[q].aoff == 0 : fl[q].aoff == fl[q - 1].aoff + fl[q - 1].H * fl[q - 1].W * fl[q - 1].aloc);
-                            fl[q].sbase = rows;
-                            hr.hw[nsm] = fl[q].H * fl[q].W; hr.sbase[nsm] = rows; hr.grouped[nsm] = head_fused_grouped(xq, hr.hw[nsm]) ? 1 : 0;
-                            rows += hist_rows_slots(hr.hw[nsm]);
-                            ++nsm;
-                        }
-                    }
-                    hr.levels = nsm;
-                    hr.rows_per_image = rows;
-                    // the epilogue levels must be pyramid levels 0 .. nsm - 1: everything behind them -- small levels of this launch and levels that did
-                    // not join it (the V2 model's last level is a plain 1x1 conv on the grouped launches) -- stays in logit form
-                    for (int q = 0; q < nsm; ++q) prefix = prefix && p->ops[members[4 * q + 2]].level == q;
-                    // (the softmax tiles of those levels put their histogram rows behind these: the row stride of an image covers both)
-                    const int sfirst = nsm < d.n_levels ? p->level_off[nsm] : d.num_anchors;
-                    hp.rows_per_image = rows + dn_cdiv(d.num_anchors - sfirst, 64);
-                    with_post = prefix && nsm > 0 && hp.rows_per_image <= pb.tiles && head_fused_post_supported(fl, nl, hp);
-                    if (with_post) {
-                        scores_ready = true; fused_rows = hr;
-                        small_first = sfirst;
-                    }
-                }
-                rc = launch_head_fused(fl, nl, xq, hs, with_post ? &hp : nullptr);
-                if (rc != DN_OK) return rc;
-                for (int q : members) hnote(q, seg);
-                ++seg;
-                if (rec && seg < p->ops.size()) (void)hipEventRecord(p->events[ev++], hs);
-                // what did not join (the V2 model's last level is a plain 1x1 conv) takes the grouped launches below
-                auto drop = [&](std::vector<int>& v) {
-                    std::vector<int> keep;
-                    for (int q : v) if (std::find(members.begin(), members.end(), q) == members.end()) keep.push_back(q);
-                    v.swap(keep);
-                };
-                drop(h_dw); drop(h_cls); drop(h_reg);
-                if (h_cls.empty() && h_reg.empty() && h_dw.empty()) return DN_OK;
-            }
-        }
-        if (!h_dw.empty()) {
-            DwArgs arr[12];
-            for (size_t q = 0; q < h_dw.size(); ++q) arr[q] = make_dw(p->ops[h_dw[q]]);
-            rc = launch_depthwise_group(arr, (int)h_dw.size(), hs);
-            if (rc != DN_OK) return rc;
-            for (int q : h_dw) hnote(q, seg);
-            ++seg;
-            if (rec) (void)hipEventRecord(p->events[ev++], hs);
-        }
-        // box and class heads of all levels in ONE launch when they fit (a dependent launch costs ~4.5 us even when empty, and
-        // the narrow box heads then share the class heads' tile instead of running as a launch of their own)
-        const bool merge_heads = dn_knob("DN_HEAD_MERGE", 1) != 0;
-        // (dense-conv heads leave in a narrow and a wide launch of at most 12 problems each, so 7 levels x 2 heads still go together --
-        // the box heads of the large levels must meet their class heads to ride in their tiles: 0.45 ms per 16 images on ssd512)
-        const bool conv_heads = !h_reg.empty() && p->ops[h_reg[0]].type == DN_OP_CONV;
-        const bool one = merge_heads && !h_reg.empty() && !h_cls.empty() && p->ops[h_reg[0]].type == p->ops[h_cls[0]].type &&
-                         (h_reg.size() + h_cls.size() <= 12 || (conv_heads && h_reg.size() <= 12 && h_cls.size() <= 12));
-        for (int kind = 0; kind < 2; ++kind) {
-            std::vector<int> lst = kind ? h_cls : h_reg;
-            if (one) {
-                if (kind == 1) break;
-                lst.insert(lst.end(), h_cls.begin(), h_cls.end());
-            }
-            if (lst.empty()) continue;
-            std::vector<PwArgs> arr(lst.size());
-            const bool conv = p->ops[lst[0]].type == DN_OP_CONV;
-            int cnt = 0;
-            std::vector<int> grouped;
-            std::set<int> taken;
-            // wide heads first, so that a box head that rides along is known before the groups are formed
-            std::stable_sort(lst.begin(), lst.end(), [&](int x, int y) { return p->ops[x].cout > p->ops[y].cout; });
-            for (size_t q = 0; q < lst.size(); ++q) {
-                PwArgs pa = conv ? conv_to_pw(make_conv(p->ops[lst[q]])) : make_pw(p->ops[lst[q]]);
-                if (conv && taken.count(lst[q])) continue;          // rides in another head's launch
-                if (conv && conv_head_big_supported(pa)) {
-                    // the wide dense heads of the large levels: MFMA-bound, each on the run-staged 256x256 tile. The box head of the
-                    // same level (same input, 16 / 24 channels) fits in the idle part of its last channel tile.
-                    int rider = -1;
-                    for (size_t u = 0; u < lst.size() && rider < 0; ++u) {
-                        const dn_op_desc &ou = p->ops[lst[u]], &oq = p->ops[lst[q]];
-                        if (u != q && !taken.count(lst[u]) && ou.in == oq.in && ou.type == oq.type && ou.k == oq.k && ou.stride == oq.stride &&
-                            ou.pad == oq.pad && ou.dil == oq.dil && ou.act == oq.act && ou.cout < oq.cout &&
-                            dn_cdiv(oq.cout + ou.cout, 256) == dn_cdiv(oq.cout, 256))
-                            rider = (int)u;
-                    }
-                    if (rider >= 0) {
-                        // the tile is chosen from cout + cout_b: the rider joins only if the launch still has a tile WITH it (21 classes x 6 anchors =
-                        // 126 + 24 channels cross a 128-channel tile boundary and fail the narrow-tile test the class head passed alone)
-                        const PwArgs pb = conv_to_pw(make_conv(p->ops[lst[rider]]));
-                        PwArgs with = pa;
-                        with.w_b = pb.w; with.bias_b = pb.bias; with.out_b = pb.out; with.cout_b = pb.cout;
-                        with.out_b_img_stride = pb.out_img_stride; with.out_b_base = pb.out_base;
-                        if (conv_head_big_supported(with)) { pa = with; taken.insert(lst[rider]); }
-                        else rider = -1;
-                    }
-                    rc = launch_conv_head_big(pa, hs);
-                    if (rc != DN_OK) return rc;
-                    hnote(lst[q], seg);
-                    if (rider >= 0) hnote(lst[rider], seg);
-                    ++seg;
-                    if (rec && seg < p->ops.size()) (void)hipEventRecord(p->events[ev++], hs);
-                    continue;
-                }
-                arr[cnt++] = pa;
-                grouped.push_back(lst[q]);
-            }
-            if (cnt == 0) continue;
-            // once the wide heads have left, the narrow box heads (16 / 24 channels) would pay the wide tile of the remaining
-            // class heads: dense-conv groups are split into a narrow and a wide launch
-            const bool split_narrow = conv && (cnt < (int)lst.size() || cnt > 12);
-            for (int pass = 0; pass < (split_narrow ? 2 : 1); ++pass) {
-                PwArgs sub[12];
-                std::vector<int> ids;
-                int nsub = 0;
-                for (int q = 0; q < cnt; ++q) {
-                    const bool narrow = arr[q].cout <= 32;
-                    if (split_narrow && narrow != (pass == 0)) continue;
-                    DN_REQUIRE(nsub < 12, "head group: more than 12 problems in one launch");
-                    sub[nsub++] = arr[q];
-                    ids.push_back(grouped[q]);
-                }
-                if (nsub == 0) continue;
-                rc = launch_pointwise_group(sub, nsub, conv, hs);
-                if (rc != DN_OK) return rc;
-                for (int q : ids) hnote(q, seg);
-                ++seg;
-                if (rec && seg < p->ops.size()) (void)hipEventRecord(p->events[ev++], hs);
-            }
-        }
-        return DN_OK;
-    };
+    const Ctx c{p, L, ws, n, (p->xcd && n >= 8) ? (n + 7) / 8 : 0};
+    Segments sg{p, s, ev0, record};
+    HeadEpilogue ep;
     // DN_POISON=1 (correctness tooling): a launch that fills every LDS byte and vector register with NaN patterns in front of every launch of
     // the forward -- results must not change (no kernel may read LDS or registers it has not written)
     const bool poison = !record && dn_knob("DN_POISON", 0) != 0;
-    for (size_t i = 0; i < p->ops.size(); ++i) {
-        if (poison) { int prc = launch_poison(main_stream); if (prc != DN_OK) return prc; }
-        const dn_op_desc& o = p->ops[i];
-        const dn_tensor_desc& ti = p->tensors[o.in];
-        const dn_tensor_desc& to = p->tensors[o.out];
-        s = main_stream;
-        if (record) (void)hipEventRecord(p->events[ev++], s);
+    for (const Launch& l : p->launches) {
+        if (poison) { int prc = launch_poison(s); if (prc != DN_OK) return prc; }
+        sg.begin(l);
         int rc = DN_OK;
-        const unsigned char* W = p->weights_dev;
-        auto note = [&](size_t op, size_t owner) {
-            if (!record) return;
-            p->prof_kernel[op] = dn_last_kernel();
-            p->prof_owner[op] = (int)owner;
-        };
-        if ((int)i == p->head_first) {
-            // all remaining ops are head ops of the pyramid levels: three grouped launches instead of up to 28.
-            // Profiling: the three launches take the event segments of ops i, i+1, i+2 (prof_owner maps members to them).
-            size_t seg = i;
-            rc = launch_heads(0, 1 << 20, s, record, seg);
-            if (rc != DN_OK) return rc;
-            for (size_t q = seg + 1; q < p->ops.size(); ++q)
-                if (record) (void)hipEventRecord(p->events[ev++], s);
-            break;
-        }
-        if ((int)i == p->tail_first) {
-            TailArgs ta{};
-            ta.count = p->tail_end - p->tail_first;
-            ta.weights = reinterpret_cast<const half_t*>(W);
-            const dn_op_desc& o0 = p->ops[i];
-            ta.in0 = reinterpret_cast<const half_t*>(tptr(o0.in));
-            ta.in0_stride = (long)(L.tbytes[o0.in] / (size_t)L.n / 2);
-            ta.xq = xq;
-            for (int q = 0; q < ta.count; ++q) {
-                const dn_op_desc& oq = p->ops[i + q];
-                const dn_tensor_desc& tq = p->tensors[oq.in];
-                const dn_tensor_desc& uq = p->tensors[oq.out];
-                TailOp& t = ta.op[q];
-                t.type = oq.type; t.cin = oq.cin; t.cout = oq.type == DN_OP_DW ? oq.cin : oq.cout; t.k = oq.k; t.stride = oq.stride; t.pad = oq.pad;
-                t.hin = tq.h; t.win = tq.w; t.hout = uq.h; t.wout = uq.w; t.act = oq.act;
-                t.w_off = (long)((oq.type == DN_OP_PW ? oq.w2_off : oq.w_off) / 2); t.b_off = (long)oq.b_off;
-                t.out = p->tail_materialise[q] ? reinterpret_cast<half_t*>(tptr(oq.out)) : nullptr;
-                t.out_stride = (long)(L.tbytes[oq.out] / (size_t)L.n / 2);
-            }
-            rc = launch_tail(ta, n, s);
-            if (rc != DN_OK) return rc;
-            for (int q = 0; q < ta.count; ++q) note(i + q, i);
-            for (int q = 1; q < ta.count; ++q)
-                if (record) (void)hipEventRecord(p->events[ev++], s);
-            i += ta.count - 1;
-            continue;
-        }
-        if (p->fused_len[i] > 0 && p->fused_kind[i] == 8) {
-            PwArgs pa = make_pw(p->ops[i + 1]);
-            const DwArgs da = make_dw(o);
-            pa.x = da.x;                                    // (the depthwise output is not materialised)
-            if (pa.residual) pa.residual = da.x;
-            rc = launch_pw_dw_direct(pa, da, s);
-            if (rc != DN_OK) return rc;
-            note(i, i); note(i + 1, i);
-            if (record) (void)hipEventRecord(p->events[ev++], s);
-            i += 1;
-            continue;
-        }
-        if (p->fused_len[i] > 0 && p->fused_kind[i] == 4) {
-            PwArgs pa = conv_to_pw(make_conv(o));
-            if (L.toff[o.out] == (size_t)-1) pa.out = nullptr;      // (materialised only when something else reads the full-resolution map)
-            pa.pool_out = reinterpret_cast<half_t*>(tptr(p->ops[i + 1].out));
-            rc = launch_conv_pool(pa, s);
-            if (rc != DN_OK) return rc;
-            note(i, i); note(i + 1, i);
-            if (record) (void)hipEventRecord(p->events[ev++], s);
-            i += 1;
-            continue;
-        }
-        if (p->fused_len[i] > 0) {
-            const int kind = p->fused_kind[i], len = p->fused_len[i];
-            const dn_op_desc* e = (kind & 1) ? &p->ops[i] : nullptr;
-            const dn_op_desc& dwo = p->ops[i + ((kind & 1) ? 1 : 0)];
-            const dn_op_desc* pj = (kind & 2) ? &p->ops[i + len - 1] : nullptr;
-            const dn_tensor_desc& tin = p->tensors[p->ops[i].in];
-            const dn_tensor_desc& tdo = p->tensors[dwo.out];
-            ExpDwArgs a{};
-            a.x = reinterpret_cast<const half_t*>(tptr(p->ops[i].in));
-            a.out = reinterpret_cast<half_t*>(tptr(pj ? pj->out : dwo.out));
-            a.pool = dwo.pool >= 0 ? reinterpret_cast<float*>(tptr(dwo.pool)) : nullptr;
-            if (e) { a.w1 = reinterpret_cast<const half_t*>(W + e->w_off); a.b1 = reinterpret_cast<const float*>(W + e->b_off); a.act1 = e->act; }
-            a.wd = reinterpret_cast<const half_t*>(W + dwo.w_off); a.bd = reinterpret_cast<const float*>(W + dwo.b_off); a.act2 = dwo.act;
-            if (pj) { a.w3 = reinterpret_cast<const half_t*>(W + pj->w_off); a.b3 = reinterpret_cast<const float*>(W + pj->b_off); }
-            a.n = n; a.H = tin.h; a.W = tin.w; a.Ho = tdo.h; a.Wo = tdo.w;
-            a.cin = tin.c; a.cexp = dwo.cin; a.cout = pj ? pj->cout : dwo.cin;
-            a.k = dwo.k; a.stride = dwo.stride; a.pad = dwo.pad;
-            a.has_res = (pj && pj->residual >= 0) ? 1 : 0;
-            a.xq = xq;
-            rc = launch_expdw(a, s);
-            if (rc != DN_OK) return rc;
-            for (int q = 0; q < len; ++q) note(i + q, i);
-            for (int q = 1; q < len; ++q)
-                if (record) (void)hipEventRecord(p->events[ev++], s);
-            i += len - 1;
-            continue;
-        }
-        switch (o.type) {
-            case DN_OP_STEM: {
-                StemArgs a;
-                a.img = net_in;
-                a.w = reinterpret_cast<const float*>(W + o.w_off);
-                a.bias = reinterpret_cast<const float*>(W + o.b_off);
-                a.out = reinterpret_cast<half_t*>(tptr(o.out));
-                a.n = n; a.h = ti.h; a.w_ = ti.w; a.cout = o.cout; a.k = o.k; a.stride = o.stride; a.pad = o.pad; a.act = o.act;
-                a.ho = to.h; a.wo = to.w;
-                for (int c = 0; c < 3; ++c) { a.mean[c] = d.mean[c]; a.inv_std[c] = 1.0f / d.std[c]; }
-                a.xq = xq;
-                a.split_ok = p->stem_split_ok[i];
-                a.w_scale = std::ldexp(1.0f, p->stem_scale_log2[i]);
-                a.w_unscale = std::ldexp(1.0f, -p->stem_scale_log2[i]);
-                if (p->n_se_in_dw > 0) { a.zero_u32 = reinterpret_cast<unsigned*>(ws + L.secnt_off); a.zero_count = p->n_se_in_dw * n; }
-                rc = launch_stem(a, s);
-                break;
-            }
-            case DN_OP_PW:
-                rc = launch_pointwise(make_pw(o), s);
-                break;
-            case DN_OP_DW:
-                rc = launch_depthwise(make_dw(o), s);
-                break;
-            case DN_OP_SE: {
-                if (p->se_fold[i] == -2) { dn_note_kernel("(se folded into the projection)"); break; }
-                if (p->se_in_dw[i] == -2) { dn_note_kernel("(se in the tail of the depthwise launch)"); break; }
-                rc = launch_se_fc(reinterpret_cast<const float*>(tptr(o.in)), p->pool_blocks[o.in], W + o.w_off,
-                                  reinterpret_cast<const float*>(W + o.b_off), W + o.w2_off,
-                                  reinterpret_cast<const float*>(W + o.b2_off), reinterpret_cast<float*>(tptr(o.out)), n,
-                                  o.cin, o.squeeze, o.pool_pixels, s, xq);
-                break;
-            }
-            case DN_OP_CONV:
-                rc = launch_conv(make_conv(o), s);
-                break;
-            case DN_OP_MAXPOOL:
-                rc = launch_maxpool(reinterpret_cast<const half_t*>(tptr(o.in)), reinterpret_cast<half_t*>(tptr(o.out)), n,
-                                    ti.h, ti.w, ti.c, o.k, o.stride, o.pad, to.h, to.w, s);
-                break;
-            case DN_OP_L2NORM:
-                rc = launch_l2norm(reinterpret_cast<const half_t*>(tptr(o.in)), reinterpret_cast<const float*>(W + o.w_off),
-                                   reinterpret_cast<half_t*>(tptr(o.out)), (long)n * ti.h * ti.w, ti.c, s);
-                break;
+        switch (l.kind) {
+            case Launch::SINGLE: rc = run_single(c, l, net_in, s); break;
+            case Launch::EXPDW: rc = run_expdw(c, l, s); break;
+            case Launch::PW_DW: rc = run_pw_dw(c, l, s); break;
+            case Launch::CONV_POOL: rc = run_conv_pool(c, l, s); break;
+            case Launch::TAIL: rc = run_tail(c, l, s); break;
+            case Launch::HEADS: rc = run_heads(c, l, heads_only, s, sg, ep); break;
         }
         if (rc != DN_OK) return rc;
-        note(i, i);
+        if (l.kind != Launch::HEADS) {      // one kernel for all its ops
+            for (int q = l.first; q < l.first + l.len; ++q) sg.note(q);
+            sg.close();
+        }
+        sg.finish();
     }
-    s = main_stream;
     if (!heads_only) {
         PostArgs a;
-        a.logits = logits; a.reg = reg; a.anchors = p->anchors_dev;
+        a.logits = reinterpret_cast<float*>(ws + L.logits_off); a.reg = reinterpret_cast<float*>(ws + L.reg_off); a.anchors = p->anchors_dev;
         a.n = n; a.A = d.num_anchors; a.K = d.num_classes;
         a.img_h = (float)d.image_h; a.img_w = (float)d.image_w;
-        a.scale_xy = nullptr;
-        // ratio = original / network size in fp32 (transform.py:280-285), written by the resize kernel
-        if (resize) a.scale_xy = scale_xy;
+        a.scale_xy = scale_xy;      // with a resize: ratio = original / network size in fp32 (transform.py:280-285), written by the resize kernel
         a.score_thresh = d.score_thresh; a.nms_thresh = d.nms_thresh; a.topk = d.topk_candidates; a.dets = d.detections_per_img;
         a.boxes = boxes; a.scores = scores; a.labels = labels; a.counts = counts; a.kept_anchor = nullptr;
         a.packed = packed;
         a.ws = ws + L.post_off; a.ws_bytes = L.post_bytes;
-        a.xq = xq;
-        a.scores_ready = scores_ready; a.hrows = fused_rows; a.small_first = small_first;
-        if (scores_ready && p->post_ticket_slot >= 0) a.tickets = reinterpret_cast<unsigned*>(ws + L.secnt_off) + (size_t)p->post_ticket_slot * n;
-        hipEvent_t* pe = record ? &p->events[ev] : nullptr;
-        int rc = launch_postprocess(a, s, pe);
+        a.xq = c.xq;
+        a.scores_ready = ep.scores_ready; a.hrows = ep.rows; a.small_first = ep.small_first;
+        if (ep.scores_ready && p->post_ticket_slot >= 0) a.tickets = reinterpret_cast<unsigned*>(ws + L.secnt_off) + (size_t)p->post_ticket_slot * n;
+        int rc = launch_postprocess(a, s, record ? &p->events[ev0 + p->ops.size()] : nullptr);
         if (rc) return rc;
-        ev += 5;
-    } else if (record) {
-        (void)hipEventRecord(p->events[ev++], s);
+    } else {
+        sg.record((int)p->ops.size());
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -1205,39 +1210,32 @@ static int enqueue(dn_plan* p, const float* images, int n, int h, int w, float* 
 
 // the whole forward: one chain, or batch_split() sub-batch chains forked onto branch streams (parallel graph branches when
 // captured). record = profiling: the sub-batches run back to back on `s`, each with its own block of events.
+static int enqueue_chain(dn_plan* p, const float* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,
+                         int32_t* counts, unsigned char* ws, bool heads_only, hipStream_t s, int S, int k, bool record = false);
+
 static int enqueue_all(dn_plan* p, const float* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,
                        int32_t* counts, unsigned char* ws, bool heads_only, hipStream_t s, bool record) {
     const int S = batch_split(p, n);
     if (S == 1) return enqueue(p, images, n, h, w, boxes, scores, labels, counts, ws, get_layout(p, n), heads_only, s, record, p->packed_out, 0);
-    const size_t D = (size_t)p->d.detections_per_img;
-    const int ev_stride = (int)p->ops.size() + 6;
     if (!record) DN_HIP_CHECK(hipEventRecord(p->ev_fork, s));
-    size_t n0 = 0;
     for (int k = 0; k < S; ++k) {
-        const int ns = sub_count(n, S, k);
-        const Layout& V = get_sub_layout(p, n, S, k);
         hipStream_t bs = s;
         if (!record && k > 0) {
             bs = p->branch_stream[k - 1];
             DN_HIP_CHECK(hipStreamWaitEvent(bs, p->ev_fork, 0));
         }
-        const float* sub_images = p->input_u8 ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(images) + n0 * 3 * (size_t)h * w)
-                                              : images + n0 * 3 * (size_t)h * w;
-        int rc = enqueue(p, sub_images, ns, h, w, boxes ? boxes + n0 * D * 4 : nullptr, scores ? scores + n0 * D : nullptr,
-                         labels ? labels + n0 * D : nullptr, counts ? counts + n0 : nullptr, ws, V, heads_only, bs, record,
-                         p->packed_out ? p->packed_out + n0 * (D + 1) * 6 : nullptr, k * ev_stride, k);
+        int rc = enqueue_chain(p, images, n, h, w, boxes, scores, labels, counts, ws, heads_only, bs, S, k, record);
         if (rc) return rc;
         if (!record && k > 0) DN_HIP_CHECK(hipEventRecord(p->ev_branch[k - 1], bs));
-        n0 += ns;
     }
     if (!record)
         for (int k = 1; k < S; ++k) DN_HIP_CHECK(hipStreamWaitEvent(s, p->ev_branch[k - 1], 0));
     return DN_OK;
 }
 
-// chain k of S on stream s (no fork / join): what one per-chain graph captures
+// chain k of S on stream s (no fork / join): what one per-chain graph captures; record: its own block of profiling events
 static int enqueue_chain(dn_plan* p, const float* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,
-                         int32_t* counts, unsigned char* ws, bool heads_only, hipStream_t s, int S, int k) {
+                         int32_t* counts, unsigned char* ws, bool heads_only, hipStream_t s, int S, int k, bool record) {
     const size_t D = (size_t)p->d.detections_per_img;
     size_t n0 = 0;
     for (int q = 0; q < k; ++q) n0 += sub_count(n, S, q);
@@ -1246,8 +1244,8 @@ static int enqueue_chain(dn_plan* p, const float* images, int n, int h, int w, f
     const float* sub_images = p->input_u8 ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(images) + n0 * 3 * (size_t)h * w)
                                           : images + n0 * 3 * (size_t)h * w;
     return enqueue(p, sub_images, ns, h, w, boxes ? boxes + n0 * D * 4 : nullptr, scores ? scores + n0 * D : nullptr,
-                   labels ? labels + n0 * D : nullptr, counts ? counts + n0 : nullptr, ws, V, heads_only, s, false,
-                   p->packed_out ? p->packed_out + n0 * (D + 1) * 6 : nullptr, 0, k);
+                   labels ? labels + n0 * D : nullptr, counts ? counts + n0 : nullptr, ws, V, heads_only, s, record,
+                   p->packed_out ? p->packed_out + n0 * (D + 1) * 6 : nullptr, record ? k * ((int)p->ops.size() + 6) : 0);
 }
 
 static int forward_impl(dn_plan* p, const float* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,

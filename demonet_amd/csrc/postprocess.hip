@@ -1161,11 +1161,6 @@ void post_hist_range(float score_thresh, int* hb0_out, int* nb_out, int* clamped
 }
 
 // DN_PP_FAST=0 disables the cut-off fast path (A/B and tests of the full path); DN_PP_WANT overrides the multiple of D.
-static int pp_env(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 int launch_postprocess(const PostArgs& a0, hipStream_t s, hipEvent_t* ev) {
     PostArgs a = a0;
     DN_REQUIRE(a.n > 0 && a.A > 0 && a.K >= 2, "postprocess: bad sizes n=%d A=%d K=%d", a.n, a.A, a.K);
