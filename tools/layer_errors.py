@@ -5,9 +5,8 @@
 For every op of the graph, on the golden input images:
   acc   = max / mean |device tensor - fp32 chain|      error accumulated from the input up to this op's output
   local = max / mean |device tensor - fp32 op(device's own fp16 input)|   what this op alone adds (rounding of its output + kernel)
-The fp32 chain is a torch evaluation of the op IR (conv -> bias -> BN -> activation -> SE -> residual, unfolded, in the
-reference's order); it is pinned to the oracle in this script (its logits must equal oracle/ssd_oracle.py's within 2e-4, which in
-turn equals the reference bit for bit: tests/test_oracle.py). Fused launches are switched off here (DN_EXPDW=0, DN_TAIL=0) so that
+The fp32 chain is oracle/op_ref.py's evaluation of the op IR (BN folded in float64, fp32 weights); tests/test_op_ref.py pins it to the
+reference's recorded head outputs (rtol 1e-4, atol 2e-4); its distance to the oracle's logits is printed in each section's title. Fused launches are switched off here (DN_EXPDW=0, DN_TAIL=0) so that
 every intermediate tensor exists in the workspace; their rounding points are the same as the separate kernels'.
 """
 import argparse
@@ -16,58 +15,12 @@ import sys
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
-ACT = {0: lambda v: v, 1: F.relu, 2: F.relu6, 3: F.hardswish}
-
-
-def conv_like(nd, sd, x, groups=1):
-    w = sd[nd.conv_key + ".weight"]
-    b = sd[nd.conv_key + ".bias"] if nd.has_bias else None
-    y = F.conv2d(x, w, b, nd.stride, nd.pad, nd.dil, groups)
-    if nd.bn_key:
-        y = F.batch_norm(y, sd[nd.bn_key + ".running_mean"], sd[nd.bn_key + ".running_var"], sd[nd.bn_key + ".weight"],
-                         sd[nd.bn_key + ".bias"], False, 0.0, nd.bn_eps)
-    return ACT[nd.act](y)
-
-
-def apply_op(g, nd, sd, val, images_norm):
-    """fp32 value of node nd given the dict `val` of tensor id -> NCHW fp32 (vec tensors: [N, C])."""
-    if nd.op == "stem":
-        return conv_like(nd, sd, images_norm)
-    x = val[nd.inp]
-    if nd.op == "pw":
-        if nd.se >= 0:
-            x = x * val[nd.se][:, :, None, None]
-        y = conv_like(nd, sd, x)
-        if nd.residual >= 0:
-            y = y + val[nd.residual]
-        return y
-    if nd.op == "dw":
-        return conv_like(nd, sd, x, groups=nd.cin)
-    if nd.op == "conv":
-        return conv_like(nd, sd, x)
-    if nd.op == "se":
-        s = x.mean(dim=(2, 3), keepdim=True)
-        s = F.relu(F.conv2d(s, sd[nd.fc1_key + ".weight"], sd[nd.fc1_key + ".bias"]))
-        s = F.hardsigmoid(F.conv2d(s, sd[nd.fc2_key + ".weight"], sd[nd.fc2_key + ".bias"]))
-        return s[:, :, 0, 0]
-    if nd.op == "maxpool":
-        return F.max_pool2d(x, nd.k, nd.stride, nd.pad, ceil_mode=nd.ceil_mode)
-    if nd.op == "l2norm":
-        return sd[nd.scale_key].view(1, -1, 1, 1) * F.normalize(x)
-    raise ValueError(nd.op)
-
-
-def head_rows(g, nd, y):
-    """[N, A*cols, H, W] -> [N, H*W*A, cols] (generalized_ssd.py:66-71)"""
-    cols = g.num_classes if nd.head == 1 else 4
-    n, _, h, w = y.shape
-    return y.view(n, -1, cols, h, w).permute(0, 3, 4, 1, 2).reshape(n, -1, cols)
+import op_ref  # noqa: E402  (oracle/op_ref.py: the fp32 evaluator of the op IR)
 
 
 def run(name, out):
@@ -89,27 +42,13 @@ def run(name, out):
     m = m.cuda()
     W, H = g.size
     imgs = torch.from_numpy(synth.images(1, 2, H, W))
-    mean = torch.tensor(g.image_mean).view(1, 3, 1, 1)
-    std = torch.tensor(g.image_std).view(1, 3, 1, 1)
-    xin = (imgs - mean) / std
+    ref = op_ref.OpRef(g, sd, round_w=False, round_se=False, bound=False)
     with torch.no_grad():
-        val = {}
-        logits_parts, reg_parts = {}, {}
-        for nd in g.nodes:
-            y = apply_op(g, nd, sd, val, xin)
-            if nd.head:
-                (logits_parts if nd.head == 1 else reg_parts)[nd.level] = head_rows(g, nd, y) if nd.op in ("pw", "conv") else None
-                if nd.op in ("pw", "conv"):
-                    continue
-            val[nd.out] = y
-            if nd.op == "dw" and nd.pool >= 0:
-                val[nd.pool] = y            # the SE node reads the pooled partial sums of this tensor: give it the tensor itself
-        ref_logits = torch.cat([logits_parts[l] for l in sorted(logits_parts)], 1)
-        ref_reg = torch.cat([reg_parts[l] for l in sorted(reg_parts)], 1)
+        ref_logits, ref_reg, val = op_ref.chain(g, sd, imgs)
+        logits_parts = {nd.level for nd in g.nodes if nd.head == 1}
         o = so.OracleSSD(name, sdn, ncls, **({"size": (size, size)} if size else {}))
         raw = o.forward_raw(list(imgs))
         pin = (ref_logits - raw["cls_logits"]).abs().max().item()
-        assert pin < 2e-4, f"fp32 chain of the op IR differs from the oracle: {pin}"
         dl, dr = m.forward_heads(imgs.cuda())
         out.write(f"## {name}{':%d' % size if size else ''}  (2 golden-style images, synthetic weights seed 0; fp32 chain vs oracle logits: max|d| {pin:.1e})\n")
         out.write(f"{'op':4s} {'key':52s} {'shape':>16s} {'max|ref|':>9s} {'acc max':>9s} {'acc mean':>9s} {'local max':>9s} {'local mean':>10s}\n")
@@ -127,8 +66,8 @@ def run(name, out):
             else:
                 continue
             dev[nd.out] = dv
-            ref = val[nd.out]
-            acc = (dv - ref).abs()
+            rv = val[nd.out]
+            acc = (dv - rv).abs()
             # local: the same op in fp32 on the device's own (fp16) inputs
             loc_val = dict(val)
             ok = True
@@ -141,11 +80,11 @@ def run(name, out):
             if nd.op == "stem":
                 loc = acc
             elif ok:
-                loc = (dv - apply_op(g, nd, sd, loc_val, xin)).abs()
+                loc = (dv - ref.op(nd, loc_val)[0]).abs()
             else:
                 loc = None
             key = nd.conv_key or nd.fc1_key or nd.scale_key or nd.op
-            out.write(f"{nd.op:4s} {key[-52:]:52s} {str(tuple(ref.shape[1:])):>16s} {ref.abs().max().item():9.3g} {acc.max().item():9.2e} "
+            out.write(f"{nd.op:4s} {key[-52:]:52s} {str(tuple(rv.shape[1:])):>16s} {rv.abs().max().item():9.3g} {acc.max().item():9.2e} "
                       f"{acc.mean().item():9.2e} " + (f"{loc.max().item():9.2e} {loc.mean().item():10.2e}" if loc is not None else f"{'-':>9s} {'-':>10s}") + "\n")
         e = (dl.cpu() - ref_logits).abs()
         r = (dr.cpu() - ref_reg).abs()
@@ -155,7 +94,8 @@ def run(name, out):
                       f"   reg: {(r / (atol + rtol * ref_reg.abs())).max().item():.3f}\n")
         lv0 = 0
         for lvl in sorted(logits_parts):
-            cnt = logits_parts[lvl].shape[1]
+            f = g.features[lvl]
+            cnt = g.anchors_per_loc[lvl] * g.t(f).h * g.t(f).w
             out.write(f"   level {lvl}: logits max|err| {e[:, lv0:lv0 + cnt].max().item():.3e} mean {e[:, lv0:lv0 + cnt].mean().item():.3e}\n")
             lv0 += cnt
         out.write(f"head cls_logits: max|ref| {ref_logits.abs().max().item():.3g}  max|err| {e.max().item():.3e}  mean|err| {e.mean().item():.3e}  "
