@@ -62,6 +62,10 @@ _SIGNATURES = {
     "dn_expand_depthwise_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "dn_ssd_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "dn_ssd_loss": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float, C.c_float] + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dn_ssd_loss_state_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "dn_ssd_loss_train": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float, C.c_float] + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
+    "dn_ssd_loss_backward": (C.c_int, [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3),
     "dn_set_graph_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "dn_set_packed_output": (C.c_int, [C.c_void_p, C.c_void_p]),
     "dn_profile_begin": (C.c_int, [C.c_void_p]),

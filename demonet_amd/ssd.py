@@ -358,10 +358,12 @@ class SSD(_Tracked):
 
     def compute_loss(self, targets: List[Dict[str, Tensor]], head_outputs: Dict[str, Tensor], anchors=None, matched_idxs=None,
                      iou_thresh: float = 0.5, positive_fraction: float = 0.25) -> Dict[str, Tensor]:
-        """The VALUE of the training loss (generalized_ssd.py:210-269 on the matching of :316-330), computed on the GPU by
-        dn_ssd_loss (demonet_amd/loss.py); no gradients -- training itself stays out of scope. `anchors` defaults to the model's
-        own default boxes; `matched_idxs`, which the reference's forward computes and passes in, is recomputed here and, when
-        given, checked against."""
+        """The training loss (generalized_ssd.py:210-269 on the matching of :316-330), computed on the GPU by dn_ssd_loss
+        (demonet_amd/loss.py). When head_outputs['cls_logits'] or ['bbox_regression'] requires grad, the returned losses are
+        differentiable with respect to them (dn_ssd_loss_train / dn_ssd_loss_backward), so any PyTorch head can be trained against
+        this loss; the backward through this model's own fp16 backbone stays out of scope. `anchors` defaults to the model's own
+        default boxes; `matched_idxs`, which the reference's forward computes and passes in, is recomputed here and, when given,
+        checked against."""
         from .loss import ssd_loss
         dev = head_outputs["cls_logits"].device
         if anchors is None:
@@ -390,7 +392,7 @@ class SSD(_Tracked):
             if targets is None:
                 raise ValueError("In training mode, targets should be passed")     # generalized_ssd.py:273-274
             raise NotImplementedError("demonet_amd implements the inference path only (SURVEY.md section 8); the loss VALUE of a batch "
-                                      "is available through SSD.loss(images, targets) / compute_loss (no gradients)")
+                                      "is available through SSD.loss(images, targets) / compute_loss (differentiable w.r.t. the head outputs it is given)")
         legacy = isinstance(images, Tensor) and images.dim() == 4                   # hub call form model(x[1,3,S,S], shapes)
         if legacy:
             images = list(images.unbind(0))

@@ -186,7 +186,7 @@ DN_API int dn_batch_split(const dn_plan* plan, int n);
  * the cached graphs: call it before sizing workspaces, with no forward of this plan in flight. */
 DN_API int dn_set_chains(dn_plan* plan, int chains);
 
-/* SSD training loss, forward value only (no gradients). Replaces, per batch: the matching of
+/* SSD training loss, the value (with its gradient: dn_ssd_loss_train below). Replaces, per batch: the matching of
  * generalized_ssd.py:316-330 (torchvision box_iou -> SSDMatcher, _utils.py:264-294,348-362) and SSD.compute_loss
  * (generalized_ssd.py:210-269: encode_boxes _utils.py:100-133, smooth_l1_loss(sum), cross_entropy(none), hard negative mining with
  * neg_to_pos_ratio * (#label > 0) negatives per image, both sums / max(1, #matched anchors)).
@@ -199,6 +199,28 @@ DN_API int dn_ssd_loss(const float* cls_logits_dev, const float* bbox_regression
                        const float* gt_boxes_dev, const int64_t* gt_labels_dev, const int32_t* gt_counts_dev,
                        int n, int num_anchors, int num_classes, int gmax, float iou_thresh, float neg_to_pos_ratio,
                        int64_t* matched_idxs_dev, float* losses_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The same loss with its gradient for both head outputs (the gradients stop there: no backward through the heads or the backbone).
+ * dn_ssd_loss_train = dn_ssd_loss (the same launches: losses_dev and matched_idxs_dev are bit-identical to it) that also keeps, in
+ * state_dev (dn_ssd_loss_state_bytes(n, A) bytes, 16-byte aligned, the caller's until the backward has run), what the backward needs:
+ * the matched index, the weight w in {0, 1, 2} of every anchor's cross entropy = (label > 0) + (mined negative), and
+ * N = max(1, #matched). The mined negatives are those of a stable descending sort (ties at the cut in anchor order), as the oracle's.
+ * dn_ssd_loss_backward, given the same inputs, that state and grad_losses_dev [2] = the upstream gradients of
+ * {bbox_regression, classification}, writes every element of
+ *   grad_cls_logits_dev [n][A][K]      = g_cls * w * (softmax(row) - onehot(target)) / N   (exactly 0 where w = 0)
+ *   grad_bbox_regression_dev [n][A][4] = g_box * clamp(p - encoded target, -1, 1) / N for matched anchors, 0 elsewhere.
+ * Either gradient pointer may be NULL (that gradient is not computed, and its input may then be NULL too); both 16-byte aligned.
+ * grad_losses_dev and N are read on the device: neither call synchronises with the host, both can be captured. Deterministic. */
+DN_API size_t dn_ssd_loss_state_bytes(int n, int num_anchors);
+DN_API int dn_ssd_loss_train(const float* cls_logits_dev, const float* bbox_regression_dev, const float* anchors_dev,
+                             const float* gt_boxes_dev, const int64_t* gt_labels_dev, const int32_t* gt_counts_dev,
+                             int n, int num_anchors, int num_classes, int gmax, float iou_thresh, float neg_to_pos_ratio,
+                             int64_t* matched_idxs_dev, float* losses_dev, void* workspace_dev, size_t workspace_bytes,
+                             void* state_dev, size_t state_bytes, void* stream);
+DN_API int dn_ssd_loss_backward(const float* cls_logits_dev, const float* bbox_regression_dev, const float* anchors_dev,
+                                const float* gt_boxes_dev, const int64_t* gt_labels_dev, const void* state_dev, size_t state_bytes,
+                                const float* grad_losses_dev, int n, int num_anchors, int num_classes, int gmax,
+                                float* grad_cls_logits_dev, float* grad_bbox_regression_dev, void* stream);
 
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
