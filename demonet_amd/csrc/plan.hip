@@ -74,13 +74,36 @@ struct Layout {
     size_t secnt_off = 0;       // [n_se_in_dw][n] unsigned: last-workgroup counters of the squeeze-excitation tails
 };
 
-struct GraphKey {
-    const void* img; int n, h, w; void* ws; void* boxes; void* scores; void* labels; void* counts; int heads_only; void* packed;
-    int chain;          // sub-batch chain index (one single-chain graph per sub-batch), -1: the whole forward in one graph
-    bool operator<(const GraphKey& o) const {
-        return std::tie(img, n, h, w, ws, boxes, scores, labels, counts, heads_only, packed, chain) <
-               std::tie(o.img, o.n, o.h, o.w, o.ws, o.boxes, o.scores, o.labels, o.counts, o.heads_only, o.packed, o.chain);
+// images of sub-batch chain k of S in a forward of n (batch_split)
+static int sub_count(int n, int S, int k) { const int base = n / S, rem = n % S; return base + (k < rem ? 1 : 0); }
+
+// What one forward was asked to do: forward_impl fills it once, everything below takes it whole.
+struct Call {
+    const void* images; bool u8;    // [n][3][h][w] fp32 planar, or with u8 [n][h][w][3] uint8 (dn_forward_u8)
+    int n, h, w;
+    float* boxes; float* scores; int64_t* labels; int32_t* counts;      // null with heads_only
+    float* packed;                  // optional extra output of the merge kernel: the plan's dn_set_packed_output setting when the call began
+    unsigned char* ws; bool heads_only;
+    // the call of sub-batch chain k of S (D = detections_per_img): the one place that knows the per-image strides of its arrays
+    Call chain(int S, int k, size_t D) const {
+        size_t n0 = 0;
+        for (int q = 0; q < k; ++q) n0 += sub_count(n, S, q);
+        Call c = *this;
+        c.n = sub_count(n, S, k);
+        c.images = static_cast<const char*>(images) + n0 * 3 * (size_t)h * w * (u8 ? 1 : sizeof(float));
+        if (!heads_only) { c.boxes += n0 * D * 4; c.scores += n0 * D; c.labels += n0 * D; c.counts += n0; }     // (all four are set: forward_impl)
+        if (packed) c.packed += n0 * (D + 1) * 6;
+        return c;
     }
+};
+
+struct GraphKey {
+    Call c;
+    int chain;          // sub-batch chain index (one single-chain graph per sub-batch), -1: the whole forward in one graph
+    auto fields() const {
+        return std::make_tuple(c.images, c.n, c.h, c.w, c.ws, c.boxes, c.scores, c.labels, c.counts, (c.heads_only ? 1 : 0) | (c.u8 ? 2 : 0), c.packed, chain);
+    }
+    bool operator<(const GraphKey& o) const { return fields() < o.fields(); }
 };
 
 // One kernel launch of the forward over ops [first, first + len). dn_create builds the list once; the workspace layout takes its
@@ -130,8 +153,7 @@ struct dn_plan {
     hipEvent_t ev_fork = nullptr, ev_branch[3] = {nullptr, nullptr, nullptr};
     std::map<std::pair<int, int>, Layout> sub_layouts;
     int chains_override = 0;                // dn_set_chains: > 0 = that many sub-batch chains per forward whatever the batch size
-    float* packed_out = nullptr;            // optional extra output of the merge kernel (dn_set_packed_output)
-    bool input_u8 = false;                  // the current call's images are [n][h][w][3] uint8 (dn_forward_u8)
+    float* packed_out = nullptr;            // dn_set_packed_output: what the next forwards copy into Call::packed
     std::vector<Launch> launches;           // the forward's kernel launches in order (dn_create), covering every op once
     int n_se_in_dw = 0;                     // depthwise launches computing an SE in their tail; slot q of the counter block belongs to the q-th
     int post_ticket_slot = -1;              // slot of the counter block lent to launch_postprocess (PostArgs::tickets); needs the stem launch that zeroes the block
@@ -142,7 +164,7 @@ struct dn_plan {
     std::vector<std::string> prof_kernel;   // label of the launch each op took part in
     std::vector<int> prof_owner;            // op index whose event segment holds that launch's time
     int prof_runs = 0;
-    // packed_out / input_u8 / the graph cache are per-plan mutable state set around a call: a plan serves ONE host thread at a time
+    // the graph cache and the stored packed_out setting are per-plan mutable state: a plan serves ONE host thread at a time
     // (several forwards in flight are several STREAMS fed by one thread, pipeline.py). A second thread entering gets DN_E_INVALID.
     std::atomic<int> in_call{0};
 };
@@ -165,7 +187,6 @@ static int batch_split(const dn_plan* p, int n) {
     if (p->split <= 1 || n < 32) return 1;
     return p->split;
 }
-static int sub_count(int n, int S, int k) { const int base = n / S, rem = n % S; return base + (k < rem ? 1 : 0); }
 
 static int level_of(const dn_plan* p, int t) {
     for (int l = 0; l < p->d.n_levels; ++l) if (p->d.level_tensor[l] == t) return l;
@@ -1134,18 +1155,18 @@ static int run_heads(const Ctx& c, const Launch& l, bool heads_only, hipStream_t
     return run_head_groups(c, h_dw, h_cls, h_reg, s, sg);
 }
 
-static int enqueue(dn_plan* p, const float* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,
-                   int32_t* counts, unsigned char* ws, const Layout& L, bool heads_only, hipStream_t s, bool record,
-                   float* packed, int ev0 = 0) {
+static int enqueue(dn_plan* p, const Call& call, const Layout& L, hipStream_t s, bool record, int ev0 = 0) {
     const dn_model_desc& d = p->d;
-    const float* net_in = images;
+    const int n = call.n, h = call.h, w = call.w;
+    unsigned char* const ws = call.ws;
+    const float* net_in = static_cast<const float*>(call.images);
     const bool resize = (h != d.image_h || w != d.image_w);
     float* scale_xy = nullptr;
-    if (p->input_u8) {
+    if (call.u8) {
         // uint8 HWC decoder output: /255, bilinear resize and HWC -> planar in one pass (the stem then normalises on load)
         float* rz = reinterpret_cast<float*>(ws + L.resized_off);
         if (resize) scale_xy = reinterpret_cast<float*>(ws + L.scale_off);
-        int rc = launch_u8hwc_to_planar(reinterpret_cast<const unsigned char*>(images), rz, scale_xy, n, h, w, d.image_h, d.image_w, s);
+        int rc = launch_u8hwc_to_planar(static_cast<const unsigned char*>(call.images), rz, scale_xy, n, h, w, d.image_h, d.image_w, s);
         if (rc) return rc;
         net_in = rz;
     } else if (resize) {
@@ -1153,7 +1174,7 @@ static int enqueue(dn_plan* p, const float* images, int n, int h, int w, float* 
         // normalising on load in the stem equals transform.py:113-114 (normalize then resize) up to fp32 rounding.
         float* rz = reinterpret_cast<float*>(ws + L.resized_off);
         scale_xy = reinterpret_cast<float*>(ws + L.scale_off);
-        int rc = launch_resize_bilinear(images, rz, scale_xy, n, h, w, d.image_h, d.image_w, s);
+        int rc = launch_resize_bilinear(net_in, rz, scale_xy, n, h, w, d.image_h, d.image_w, s);
         if (rc) return rc;
         net_in = rz;
     }
@@ -1173,7 +1194,7 @@ static int enqueue(dn_plan* p, const float* images, int n, int h, int w, float* 
             case Launch::PW_DW: rc = run_pw_dw(c, l, s); break;
             case Launch::CONV_POOL: rc = run_conv_pool(c, l, s); break;
             case Launch::TAIL: rc = run_tail(c, l, s); break;
-            case Launch::HEADS: rc = run_heads(c, l, heads_only, s, sg, ep); break;
+            case Launch::HEADS: rc = run_heads(c, l, call.heads_only, s, sg, ep); break;
         }
         if (rc != DN_OK) return rc;
         if (l.kind != Launch::HEADS) {      // one kernel for all its ops
@@ -1182,15 +1203,15 @@ static int enqueue(dn_plan* p, const float* images, int n, int h, int w, float* 
         }
         sg.finish();
     }
-    if (!heads_only) {
+    if (!call.heads_only) {
         PostArgs a;
         a.logits = reinterpret_cast<float*>(ws + L.logits_off); a.reg = reinterpret_cast<float*>(ws + L.reg_off); a.anchors = p->anchors_dev;
         a.n = n; a.A = d.num_anchors; a.K = d.num_classes;
         a.img_h = (float)d.image_h; a.img_w = (float)d.image_w;
         a.scale_xy = scale_xy;      // with a resize: ratio = original / network size in fp32 (transform.py:280-285), written by the resize kernel
         a.score_thresh = d.score_thresh; a.nms_thresh = d.nms_thresh; a.topk = d.topk_candidates; a.dets = d.detections_per_img;
-        a.boxes = boxes; a.scores = scores; a.labels = labels; a.counts = counts; a.kept_anchor = nullptr;
-        a.packed = packed;
+        a.boxes = call.boxes; a.scores = call.scores; a.labels = call.labels; a.counts = call.counts; a.kept_anchor = nullptr;
+        a.packed = call.packed;
         a.ws = ws + L.post_off; a.ws_bytes = L.post_bytes;
         a.xq = c.xq;
         a.scores_ready = ep.scores_ready; a.hrows = ep.rows; a.small_first = ep.small_first;
@@ -1208,15 +1229,17 @@ static int enqueue(dn_plan* p, const float* images, int n, int h, int w, float* 
     return DN_OK;
 }
 
+// chain k of S on stream s (no fork / join): what one per-chain graph captures; record: its own block of profiling events
+static int enqueue_chain(dn_plan* p, const Call& call, hipStream_t s, int S, int k, bool record = false) {
+    const int ev0 = record ? k * ((int)p->ops.size() + 6) : 0;
+    return enqueue(p, call.chain(S, k, (size_t)p->d.detections_per_img), get_sub_layout(p, call.n, S, k), s, record, ev0);
+}
+
 // the whole forward: one chain, or batch_split() sub-batch chains forked onto branch streams (parallel graph branches when
 // captured). record = profiling: the sub-batches run back to back on `s`, each with its own block of events.
-static int enqueue_chain(dn_plan* p, const float* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,
-                         int32_t* counts, unsigned char* ws, bool heads_only, hipStream_t s, int S, int k, bool record = false);
-
-static int enqueue_all(dn_plan* p, const float* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,
-                       int32_t* counts, unsigned char* ws, bool heads_only, hipStream_t s, bool record) {
-    const int S = batch_split(p, n);
-    if (S == 1) return enqueue(p, images, n, h, w, boxes, scores, labels, counts, ws, get_layout(p, n), heads_only, s, record, p->packed_out, 0);
+static int enqueue_all(dn_plan* p, const Call& call, hipStream_t s, bool record) {
+    const int S = batch_split(p, call.n);
+    if (S == 1) return enqueue(p, call, get_layout(p, call.n), s, record);
     if (!record) DN_HIP_CHECK(hipEventRecord(p->ev_fork, s));
     for (int k = 0; k < S; ++k) {
         hipStream_t bs = s;
@@ -1224,7 +1247,7 @@ static int enqueue_all(dn_plan* p, const float* images, int n, int h, int w, flo
             bs = p->branch_stream[k - 1];
             DN_HIP_CHECK(hipStreamWaitEvent(bs, p->ev_fork, 0));
         }
-        int rc = enqueue_chain(p, images, n, h, w, boxes, scores, labels, counts, ws, heads_only, bs, S, k, record);
+        int rc = enqueue_chain(p, call, bs, S, k, record);
         if (rc) return rc;
         if (!record && k > 0) DN_HIP_CHECK(hipEventRecord(p->ev_branch[k - 1], bs));
     }
@@ -1233,22 +1256,22 @@ static int enqueue_all(dn_plan* p, const float* images, int n, int h, int w, flo
     return DN_OK;
 }
 
-// chain k of S on stream s (no fork / join): what one per-chain graph captures; record: its own block of profiling events
-static int enqueue_chain(dn_plan* p, const float* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,
-                         int32_t* counts, unsigned char* ws, bool heads_only, hipStream_t s, int S, int k, bool record) {
-    const size_t D = (size_t)p->d.detections_per_img;
-    size_t n0 = 0;
-    for (int q = 0; q < k; ++q) n0 += sub_count(n, S, q);
-    const int ns = sub_count(n, S, k);
-    const Layout& V = get_sub_layout(p, n, S, k);
-    const float* sub_images = p->input_u8 ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(images) + n0 * 3 * (size_t)h * w)
-                                          : images + n0 * 3 * (size_t)h * w;
-    return enqueue(p, sub_images, ns, h, w, boxes ? boxes + n0 * D * 4 : nullptr, scores ? scores + n0 * D : nullptr,
-                   labels ? labels + n0 * D : nullptr, counts ? counts + n0 : nullptr, ws, V, heads_only, s, record,
-                   p->packed_out ? p->packed_out + n0 * (D + 1) * 6 : nullptr, record ? k * ((int)p->ops.size() + 6) : 0);
+// one graph executable of `call` on the plan's capture stream: chain `chain` of S alone, or with chain < 0 the whole forward
+static int capture(dn_plan* p, const Call& call, int S, int chain, hipGraphExec_t* out) {
+    hipGraph_t g = nullptr;
+    if (!p->capture_stream) DN_HIP_CHECK(hipStreamCreateWithFlags(&p->capture_stream, hipStreamNonBlocking));
+    DN_HIP_CHECK(hipStreamBeginCapture(p->capture_stream, hipStreamCaptureModeThreadLocal));
+    const int rc = chain < 0 ? enqueue_all(p, call, p->capture_stream, false) : enqueue_chain(p, call, p->capture_stream, S, chain);
+    hipError_t e = hipStreamEndCapture(p->capture_stream, &g);
+    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+    if (e != hipSuccess) { dn_set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return DN_E_HIP; }
+    e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (e != hipSuccess) { dn_set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); return DN_E_HIP; }
+    return DN_OK;
 }
 
-static int forward_impl(dn_plan* p, const float* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,
+static int forward_impl(dn_plan* p, const void* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,
                         int32_t* counts, void* workspace, size_t ws_bytes, void* stream, bool heads_only, bool u8 = false) {
     DN_REQUIRE(p && images && workspace, "dn_forward: null argument");
     DN_REQUIRE(n > 0 && h > 0 && w > 0, "dn_forward: bad shape n=%d h=%d w=%d", n, h, w);
@@ -1258,8 +1281,6 @@ static int forward_impl(dn_plan* p, const float* images, int n, int h, int w, fl
         ~Busy() { if (ok) f.store(0); }
     } busy(p->in_call);
     DN_REQUIRE(busy.ok, "dn_forward: the plan is in use by another host thread (one plan serves one thread at a time; use one plan per thread)");
-    // per-call state of the plan: set and cleared INSIDE the guard (a second thread that the guard rejects must not have touched it)
-    struct U8 { dn_plan* p; U8(dn_plan* q, bool v) : p(q) { p->input_u8 = v; } ~U8() { p->input_u8 = false; } } u8_state(p, u8);
     DN_REQUIRE(heads_only || (boxes && scores && labels && counts), "dn_forward: null output buffer");
     const Layout& L = get_layout(p, n);
     if (ws_bytes < L.total) {
@@ -1267,10 +1288,11 @@ static int forward_impl(dn_plan* p, const float* images, int n, int h, int w, fl
         return DN_E_WORKSPACE;
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
+    // (inside the guard: dn_set_packed_output refuses to change the stored setting while a call is in progress)
+    const Call call{images, u8, n, h, w, boxes, scores, labels, counts, p->packed_out, reinterpret_cast<unsigned char*>(workspace), heads_only};
     p->heads_partial[workspace] = !heads_only;
+    const int S = batch_split(p, n);
     if (p->profiling) {
-        const int S = batch_split(p, n);
         const size_t stride = p->ops.size() + 6;
         const size_t need = stride * S;
         while (p->events.size() < need) {
@@ -1280,7 +1302,7 @@ static int forward_impl(dn_plan* p, const float* images, int n, int h, int w, fl
         }
         p->prof_kernel.assign(p->ops.size(), "");
         p->prof_owner.assign(p->ops.size(), -1);
-        int rc = enqueue_all(p, images, n, h, w, boxes, scores, labels, counts, ws, heads_only, s, true);
+        int rc = enqueue_all(p, call, s, true);
         if (rc) return rc;
         DN_HIP_CHECK(hipStreamSynchronize(s));
         const size_t nseg = heads_only ? p->ops.size() : p->ops.size() + 4;      // + softmax/decode | cut-off + selection | merge | fallback
@@ -1294,7 +1316,7 @@ static int forward_impl(dn_plan* p, const float* images, int n, int h, int w, fl
         p->prof_runs++;
         return DN_OK;
     }
-    if (!p->graph_mode) return enqueue_all(p, images, n, h, w, boxes, scores, labels, counts, ws, heads_only, s, false);
+    if (!p->graph_mode) return enqueue_all(p, call, s, false);
 
     // Default: the sub-batch chains are parallel branches of ONE graph. DN_CHAIN_GRAPHS=1: one single-chain hipGraph per
     // sub-batch, each replayed on a stream of its own (the caller's and the plan's branch streams, forked / joined with events
@@ -1302,56 +1324,31 @@ static int forward_impl(dn_plan* p, const float* images, int n, int h, int w, fl
     // each queue pays its own 1.7 us per dependent launch, while the branches of one graph pay ~2.9 us per launch one after
     // another; on the real chain the two forms measure the same at two chains (1.25 vs 1.24 ms) and per-chain graphs lose
     // badly at three or four (1.9 ms): kept as an opt-in for that measurement only.
-    const int S = batch_split(p, n);
     // Measured (batch 32 = 2 x 16, 12 runs each): per-chain graphs 0.78 ms every time, one graph with two branches 0.785 ms in
     // two runs of three and 0.82 - 0.85 ms in the third (the placement of the branches differs from process to process); at batch
     // 64 one graph is 0.7 % faster (1.127 vs 1.135 ms). Default: per-chain graphs below 64 images.
     const bool want_chains = p->chain_graphs < 0 ? n < 64 : p->chain_graphs != 0;
     const bool per_chain = S > 1 && want_chains;
-    const int flags = (heads_only ? 1 : 0) | (p->input_u8 ? 2 : 0);
-    auto capture = [&](const GraphKey& key, hipGraphExec_t* out) -> int {
-        hipGraph_t g = nullptr;
-        if (!p->capture_stream) DN_HIP_CHECK(hipStreamCreateWithFlags(&p->capture_stream, hipStreamNonBlocking));
-        hipStream_t cs = p->capture_stream;
-        DN_HIP_CHECK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        int rc;
-        if (key.chain < 0) rc = enqueue_all(p, images, n, h, w, boxes, scores, labels, counts, ws, heads_only, cs, false);
-        else rc = enqueue_chain(p, images, n, h, w, boxes, scores, labels, counts, ws, heads_only, cs, S, key.chain);
-        hipError_t e = hipStreamEndCapture(cs, &g);
-        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-        if (e != hipSuccess) { dn_set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return DN_E_HIP; }
-        e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (e != hipSuccess) { dn_set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); return DN_E_HIP; }
-        return DN_OK;
-    };
-    GraphKey key{images, n, h, w, workspace, boxes, scores, labels, counts, flags, p->packed_out, per_chain ? 0 : -1};
-    auto it = p->graphs.find(key);
+    const int G = per_chain ? S : 1;        // graphs of this call: one per chain, or one for the whole forward
+    auto it = p->graphs.find(GraphKey{call, per_chain ? 0 : -1});
     if (it == p->graphs.end()) {
         // first call with this signature: run once eagerly (sets function attributes, validates), then capture
-        int rc = enqueue_all(p, images, n, h, w, boxes, scores, labels, counts, ws, heads_only, s, false);
+        int rc = enqueue_all(p, call, s, false);
         if (rc) return rc;
-        if (p->graphs.size() + (per_chain ? S : 1) > 64)         // bound the cache (a pipeline of forwards holds one entry per slot and output set)
-            drop_graphs(p);                                      // (drains the device first: other slots may be replaying these executables)
-        for (int k = 0; k < (per_chain ? S : 1); ++k) {
-            GraphKey kk = key;
-            kk.chain = per_chain ? k : -1;
+        if (p->graphs.size() + G > 64)      // bound the cache (a pipeline of forwards holds one entry per slot and output set)
+            drop_graphs(p);                 // (drains the device first: other slots may be replaying these executables)
+        for (int k = 0; k < G; ++k) {
+            const int chain = per_chain ? k : -1;
             hipGraphExec_t ge = nullptr;
-            rc = capture(kk, &ge);
+            rc = capture(p, call, S, chain, &ge);
             if (rc) return rc;
-            p->graphs.emplace(kk, ge);
+            p->graphs.emplace(GraphKey{call, chain}, ge);
         }
         return DN_OK;       // the eager run above already produced this call's results
     }
-    if (!per_chain) {
-        DN_HIP_CHECK(hipGraphLaunch(it->second, s));
-        return DN_OK;
-    }
-    DN_HIP_CHECK(hipEventRecord(p->ev_fork, s));
-    for (int k = 1; k < S; ++k) {
-        GraphKey kk = key;
-        kk.chain = k;
-        auto itk = p->graphs.find(kk);
+    if (G > 1) DN_HIP_CHECK(hipEventRecord(p->ev_fork, s));
+    for (int k = 1; k < G; ++k) {
+        auto itk = p->graphs.find(GraphKey{call, k});
         DN_REQUIRE(itk != p->graphs.end(), "dn_forward: chain graph %d missing", k);
         hipStream_t bs = p->branch_stream[k - 1];
         DN_HIP_CHECK(hipStreamWaitEvent(bs, p->ev_fork, 0));
@@ -1359,7 +1356,7 @@ static int forward_impl(dn_plan* p, const float* images, int n, int h, int w, fl
         DN_HIP_CHECK(hipEventRecord(p->ev_branch[k - 1], bs));
     }
     DN_HIP_CHECK(hipGraphLaunch(it->second, s));
-    for (int k = 1; k < S; ++k) DN_HIP_CHECK(hipStreamWaitEvent(s, p->ev_branch[k - 1], 0));
+    for (int k = 1; k < G; ++k) DN_HIP_CHECK(hipStreamWaitEvent(s, p->ev_branch[k - 1], 0));
     return DN_OK;
 }
 
@@ -1372,7 +1369,7 @@ extern "C" int dn_forward(dn_plan* plan, const float* images_dev, int n, int h, 
 extern "C" int dn_forward_u8(dn_plan* plan, const uint8_t* images_dev, int n, int h, int w, float* boxes_dev, float* scores_dev,
                              int64_t* labels_dev, int32_t* counts_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
     DN_REQUIRE(plan, "dn_forward_u8: null plan");
-    return forward_impl(plan, reinterpret_cast<const float*>(images_dev), n, h, w, boxes_dev, scores_dev, labels_dev, counts_dev,
+    return forward_impl(plan, images_dev, n, h, w, boxes_dev, scores_dev, labels_dev, counts_dev,
                         workspace_dev, workspace_bytes, stream, false, true);
 }
 

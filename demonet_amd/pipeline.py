@@ -19,10 +19,11 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from .ssd import _require_floating, forward_args
 
 
 class _Slot:
-    __slots__ = ("stream", "images", "ws", "boxes", "scores", "labels", "counts", "packed", "done", "args", "src_ptr")
+    __slots__ = ("stream", "images", "ws", "boxes", "scores", "labels", "counts", "packed", "done", "args")
 
 
 _STREAMS = {}
@@ -68,12 +69,12 @@ class ForwardPipeline:
         self._gen = model._plan_gen
         L = _lib.lib()
         self._L = L
-        if getattr(model, "_pipe_refs", 0) > 0 and getattr(model, "_pipe_chains", chains) != chains:
+        if model._pipe_refs > 0 and model._pipe_chains != chains:
             raise ValueError("another open pipeline of this model uses chains={}".format(model._pipe_chains))
-        if getattr(model, "_pipe_refs", 0) == 0:    # (dn_set_chains drops the plan's graphs: only with no other pipeline replaying them)
+        if model._pipe_refs == 0:                   # (dn_set_chains drops the plan's graphs: only with no other pipeline replaying them)
             _lib.check(L.dn_set_chains(C.c_void_p(self._handle), int(chains)))
             model._bufs = {}                        # workspaces sized for the previous split are stale
-        model._pipe_refs = getattr(model, "_pipe_refs", 0) + 1
+        model._pipe_refs += 1
         model._pipe_chains = chains
         D = model.detections_per_img
         self._fwd = L.dn_forward_u8 if uint8 else L.dn_forward
@@ -93,7 +94,6 @@ class ForwardPipeline:
                 s.counts = torch.empty((batch,), dtype=torch.int32, device=device)
                 s.packed = torch.zeros((batch, D + 1, 6), dtype=torch.float32, device=device) if packed else None
                 s.done = torch.cuda.Event()
-                s.src_ptr = None
                 s.args = None
                 self.slots.append(s)
         self.n = 0                                  # next ticket
@@ -101,11 +101,8 @@ class ForwardPipeline:
 
     # ------------------------------------------------------------------------------------------------------
     def _args(self, s, src_ptr):
-        if s.src_ptr != src_ptr:
-            s.args = (C.c_void_p(self._handle), C.c_void_p(src_ptr), self.batch, self.h, self.w, C.c_void_p(s.boxes.data_ptr()),
-                      C.c_void_p(s.scores.data_ptr()), C.c_void_p(s.labels.data_ptr()), C.c_void_p(s.counts.data_ptr()),
-                      C.c_void_p(s.ws.data_ptr()), s.ws.numel(), C.c_void_p(s.stream.cuda_stream))
-            s.src_ptr = src_ptr
+        if s.args is None or s.args[1].value != src_ptr:
+            s.args = forward_args(self._handle, src_ptr, self.batch, self.h, self.w, (s.boxes, s.scores, s.labels, s.counts), s.ws, s.stream.cuda_stream)
         return s.args
 
     def submit(self, images: Tensor, persistent_input: bool = False) -> int:
@@ -128,8 +125,8 @@ class ForwardPipeline:
         if self.uint8:
             if images.dtype != torch.uint8:
                 raise ValueError("expected uint8 images, got {}".format(images.dtype))
-        elif not images.is_floating_point():
-            raise TypeError(f"Expected input images to be of floating type (in range [0, 1]), but found type {images.dtype} instead")
+        else:
+            _require_floating(images)
         if images.device != self.device:
             raise ValueError("images are on {}, the pipeline on {}".format(images.device, self.device))
         # the slot's previous outputs may be overwritten now, and `images` must be complete: order after the caller's stream
@@ -140,8 +137,7 @@ class ForwardPipeline:
                 s.images.copy_(images, non_blocking=True)
             images.record_stream(s.stream)
         args = self._args(s, images.data_ptr() if direct else s.images.data_ptr())
-        _lib.check(self._L.dn_set_packed_output(args[0], C.c_void_p(s.packed.data_ptr()) if s.packed is not None else None))
-        self.model._packed_set = -1                 # (the model's own forward re-sets it)
+        self.model._set_packed(s.packed)            # (the plan is the model's own: checked above)
         with torch.cuda.device(self.device):
             _lib.check(self._fwd(*args), self._name)
         s.done.record(s.stream)

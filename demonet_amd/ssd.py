@@ -7,7 +7,6 @@ into the HIP library through the C ABI (include/demonet_hip.h). There is no PyTo
 library or without a GPU the forward raises.
 """
 import ctypes as C
-import warnings
 from collections import OrderedDict
 from typing import Dict, List, Optional
 
@@ -73,6 +72,23 @@ def _attach(root: nn.Module, key: str, value: Tensor, buffer: bool):
         m.register_parameter(parts[-1], nn.Parameter(value, requires_grad=False))
 
 
+def _require_floating(t: Tensor):
+    if not t.is_floating_point():
+        raise TypeError(f"Expected input images to be of floating type (in range [0, 1]), but found type {t.dtype} instead")  # transform.py:130-134
+
+
+def _require_float_batch(images: Tensor):
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError("expected a [N,3,H,W] batch, got {}".format(tuple(images.shape)))
+    _require_floating(images)
+
+
+def forward_args(handle, src_ptr, n, h, w, outs, ws, stream):
+    """The ctypes argument tuple of dn_forward / dn_forward_u8 (include/demonet_hip.h); outs: (boxes, scores, labels, counts), stream: a raw hipStream_t."""
+    p = C.c_void_p
+    return (p(handle), p(src_ptr), n, h, w, *(p(t.data_ptr()) for t in outs), p(ws.data_ptr()), ws.numel(), p(stream))
+
+
 class SSD(_Tracked):
     def __init__(self, graph: Graph, init: str = "normal"):
         super().__init__()
@@ -113,7 +129,11 @@ class SSD(_Tracked):
         self._lowered = None
         self._bufs = {}
         self._call = None
-        self._packed_set = -1         # address last handed to dn_set_packed_output (-1: unknown)
+        self._packed_set = -1         # address the plan's dn_set_packed_output setting holds (-1: unknown): _set_packed
+        self._fast_sig = None         # _remember_weights
+        self._graph_mode = None       # set_graph_mode; None: never asked, the library's default (DN_GRAPH) holds
+        self._plan_gen = 0            # counts the plans built (a new plan may reuse the old one's address: pipelines compare this)
+        self._pipe_refs, self._pipe_chains = 0, None      # open ForwardPipelines of the current plan, and the `chains` they share
         self.eval()
 
     # ------------------------------------------------------------------------------------------------------
@@ -132,7 +152,7 @@ class SSD(_Tracked):
         """The per-call form of the test above: True when the plan in hand is still what the current weights lower to. Same criteria
         (tensor identities through the structure epoch, storage addresses, in-place version counters, the post-process settings), walked
         over a cached flat list."""
-        c = getattr(self, "_fast_sig", None)
+        c = self._fast_sig
         if c is None or c[0] != _STRUCT_EPOCH[0]:
             return False
         _, dev, hyper, tensors, ptrs, vers = c
@@ -180,7 +200,7 @@ class SSD(_Tracked):
         self._sig = sig
         self._remember_weights(device)
         self._bufs = {}
-        self._plan_gen = getattr(self, "_plan_gen", 0) + 1      # (a new plan may reuse the old one's address: pipelines compare this)
+        self._plan_gen += 1
         self._pipe_refs = 0
         return self._handle
 
@@ -208,22 +228,20 @@ class SSD(_Tracked):
         b = self._bufs.get(key)
         if b is None:
             L = _lib.lib()
-            D = self.detections_per_img
             ws = L.dn_workspace_bytes(C.c_void_p(self._handle), n)
             # the four outputs are typed views of ONE allocation, so that the list API takes its private copy of a call's results
             # with one device copy (forward())
             out = torch.empty(self._out_bytes(n), dtype=torch.uint8, device=device)
-            boxes, scores, labels, counts = self._out_views(out, n)
             b = dict(
                 images=torch.empty((n, 3, h, w), dtype=torch.float32, device=device),
                 ws=torch.empty(ws, dtype=torch.uint8, device=device),
-                out=out, boxes=boxes, scores=scores, labels=labels, counts=counts,
+                out=out, outs=self._out_views(out, n),       # outs: (boxes, scores, labels, counts)
             )
             if len(self._bufs) >= 4:
                 self._bufs.clear()
             self._call = None
             self._bufs[key] = b
-            if hasattr(self, "_graph_mode"):
+            if self._graph_mode is not None:
                 _lib.check(L.dn_set_graph_mode(C.c_void_p(self._handle), int(self._graph_mode)))
         return b
 
@@ -243,10 +261,7 @@ class SSD(_Tracked):
         labels [N,D] int64, counts [N] int32) that stay valid until the next call with the same shape.
         persistent_input=True promises that `images` keeps its address between calls (lets the hipGraph replay).
         packed: optional [N, D+1, 6] fp32 device tensor that additionally receives the gather payload (dist.py)."""
-        if images.dim() != 4 or images.shape[1] != 3:
-            raise ValueError("expected a [N,3,H,W] batch, got {}".format(tuple(images.shape)))
-        if not images.is_floating_point():
-            raise TypeError(f"Expected input images to be of floating type (in range [0, 1]), but found type {images.dtype} instead")
+        _require_float_batch(images)
         handle = self._plan(images.device)
         n, _, h, w = images.shape
         self._check_packed(packed, n, images.device)
@@ -258,20 +273,13 @@ class SSD(_Tracked):
             src = b["images"]
         dev = images.device
         stream = torch.cuda.current_stream(dev).cuda_stream
-        # one C call per forward: the argument tuple of (plan, buffers, input address, stream, packed output) is built once and reused
-        # while none of them changes -- a synchronous caller pays for every microsecond of Python in front of the graph launch
-        pk = packed.data_ptr() if packed is not None else 0
-        key = (handle, b["ws"].data_ptr(), src.data_ptr(), stream, pk)
-        if self._packed_set != pk:                  # (plan-global state of the library; forward_uint8 and ForwardPipeline set it too)
-            _lib.check(_lib.lib().dn_set_packed_output(C.c_void_p(handle), C.c_void_p(pk) if pk else None))
-            self._packed_set = pk
+        self._set_packed(packed)
+        # one C call per forward: the argument tuple of (plan, buffers, input address, stream) is built once and reused while none
+        # of them changes -- a synchronous caller pays for every microsecond of Python in front of the graph launch
+        key = (handle, b["ws"].data_ptr(), src.data_ptr(), stream)
         call = self._call
         if call is None or call[0] != key:
-            L = _lib.lib()
-            args = (C.c_void_p(handle), C.c_void_p(src.data_ptr()), n, h, w, C.c_void_p(b["boxes"].data_ptr()), C.c_void_p(b["scores"].data_ptr()),
-                    C.c_void_p(b["labels"].data_ptr()), C.c_void_p(b["counts"].data_ptr()), C.c_void_p(b["ws"].data_ptr()), b["ws"].numel(),
-                    C.c_void_p(stream))
-            call = self._call = (key, L.dn_forward, args, (b["boxes"], b["scores"], b["labels"], b["counts"]))
+            call = self._call = (key, _lib.lib().dn_forward, forward_args(handle, src.data_ptr(), n, h, w, b["outs"], b["ws"], stream), b["outs"])
         if torch.cuda.current_device() == dev.index:
             rc = call[1](*call[2])
         else:
@@ -290,6 +298,13 @@ class SSD(_Tracked):
             raise ValueError("packed must be a contiguous float32 tensor of shape {} on {}, got {} {} on {}".format(
                 want, device, tuple(packed.shape), packed.dtype, packed.device))
 
+    def _set_packed(self, packed: Optional[Tensor]):
+        """Make `packed` (None: nothing) the extra output of the plan's next forwards: plan-global state of the library, changed only here."""
+        pk = packed.data_ptr() if packed is not None else 0
+        if self._packed_set != pk:
+            _lib.check(_lib.lib().dn_set_packed_output(C.c_void_p(self._handle), C.c_void_p(pk) if pk else None))
+            self._packed_set = pk
+
     def forward_uint8(self, images: Tensor, packed: Optional[Tensor] = None):
         """images: [N,H,W,3] uint8 on the GPU -- a decoder's output (HWC, RGB). ToTensor (/255), the bilinear resize to the network
         size and the HWC -> planar conversion run on the device ahead of the stem (transform.py:27-53,129-138); results equal
@@ -304,14 +319,10 @@ class SSD(_Tracked):
         self._check_packed(packed, n, images.device)
         b = self._buffers_for(n, h, w, images.device)
         stream = torch.cuda.current_stream(images.device).cuda_stream
-        _lib.check(_lib.lib().dn_set_packed_output(C.c_void_p(handle), C.c_void_p(packed.data_ptr()) if packed is not None else None))
-        self._packed_set = packed.data_ptr() if packed is not None else 0
+        self._set_packed(packed)
         with torch.cuda.device(images.device):
-            _lib.check(_lib.lib().dn_forward_u8(C.c_void_p(handle), C.c_void_p(images.data_ptr()), n, h, w,
-                                                C.c_void_p(b["boxes"].data_ptr()), C.c_void_p(b["scores"].data_ptr()),
-                                                C.c_void_p(b["labels"].data_ptr()), C.c_void_p(b["counts"].data_ptr()),
-                                                C.c_void_p(b["ws"].data_ptr()), b["ws"].numel(), C.c_void_p(stream)), "dn_forward_u8")
-        return b["boxes"], b["scores"], b["labels"], b["counts"]
+            _lib.check(_lib.lib().dn_forward_u8(*forward_args(handle, images.data_ptr(), n, h, w, b["outs"], b["ws"], stream)), "dn_forward_u8")
+        return b["outs"]
 
     def batch_split(self, n: int) -> int:
         """Number of parallel sub-batch launch chains a forward of n images is issued as (1 = a single chain)."""
@@ -321,10 +332,7 @@ class SSD(_Tracked):
 
     def forward_heads(self, images: Tensor):
         """Backbone + heads only: returns (cls_logits [N,A,K], bbox_regression [N,A,4]) fp32 device tensors (copies)."""
-        if images.dim() != 4 or images.shape[1] != 3:
-            raise ValueError("expected a [N,3,H,W] batch, got {}".format(tuple(images.shape)))
-        if not images.is_floating_point():
-            raise TypeError(f"Expected input images to be of floating type (in range [0, 1]), but found type {images.dtype} instead")
+        _require_float_batch(images)
         handle = self._plan(images.device)
         n, _, h, w = images.shape
         b = self._buffers_for(n, h, w, images.device)
@@ -401,9 +409,7 @@ class SSD(_Tracked):
             if img.dim() != 3:
                 raise ValueError("images is expected to be a list of 3d tensors "
                                  "of shape [C, H, W], got {}".format(img.shape))    # transform.py:110-112
-            if not img.is_floating_point():
-                raise TypeError(f"Expected input images to be of floating type (in range [0, 1]), "
-                                f"but found type {img.dtype} instead")              # transform.py:130-134
+            _require_floating(img)
             g = groups.get(img.shape)
             if g is None:
                 groups[img.shape] = [i]
