@@ -73,6 +73,10 @@ _SIGNATURES = {
     "dn_batch_split": (C.c_int, [C.c_void_p, C.c_int]),
     "dn_set_chains": (C.c_int, [C.c_void_p, C.c_int]),
     "dn_profile_op_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32)]),
+    "dn_level_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dn_forward_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dn_lite_head_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "dn_lite_head_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_int64] + [C.c_int] * 5 + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -84,6 +84,7 @@ struct Call {
     float* boxes; float* scores; int64_t* labels; int32_t* counts;      // null with heads_only
     float* packed;                  // optional extra output of the merge kernel: the plan's dn_set_packed_output setting when the call began
     unsigned char* ws; bool heads_only;
+    bool features_only = false;     // dn_forward_features: stop in front of the head launches (implies heads_only)
     // the call of sub-batch chain k of S (D = detections_per_img): the one place that knows the per-image strides of its arrays
     Call chain(int S, int k, size_t D) const {
         size_t n0 = 0;
@@ -101,7 +102,7 @@ struct GraphKey {
     Call c;
     int chain;          // sub-batch chain index (one single-chain graph per sub-batch), -1: the whole forward in one graph
     auto fields() const {
-        return std::make_tuple(c.images, c.n, c.h, c.w, c.ws, c.boxes, c.scores, c.labels, c.counts, (c.heads_only ? 1 : 0) | (c.u8 ? 2 : 0), c.packed, chain);
+        return std::make_tuple(c.images, c.n, c.h, c.w, c.ws, c.boxes, c.scores, c.labels, c.counts, (c.heads_only ? 1 : 0) | (c.u8 ? 2 : 0) | (c.features_only ? 4 : 0), c.packed, chain);
     }
     bool operator<(const GraphKey& o) const { return fields() < o.fields(); }
 };
@@ -1185,6 +1186,7 @@ static int enqueue(dn_plan* p, const Call& call, const Layout& L, hipStream_t s,
     // the forward -- results must not change (no kernel may read LDS or registers it has not written)
     const bool poison = !record && dn_knob("DN_POISON", 0) != 0;
     for (const Launch& l : p->launches) {
+        if (call.features_only && l.kind == Launch::HEADS) continue;      // the level tensors are complete in front of the head launches
         if (poison) { int prc = launch_poison(s); if (prc != DN_OK) return prc; }
         sg.begin(l);
         int rc = DN_OK;
@@ -1272,7 +1274,7 @@ static int capture(dn_plan* p, const Call& call, int S, int chain, hipGraphExec_
 }
 
 static int forward_impl(dn_plan* p, const void* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,
-                        int32_t* counts, void* workspace, size_t ws_bytes, void* stream, bool heads_only, bool u8 = false) {
+                        int32_t* counts, void* workspace, size_t ws_bytes, void* stream, bool heads_only, bool u8 = false, bool features_only = false) {
     DN_REQUIRE(p && images && workspace, "dn_forward: null argument");
     DN_REQUIRE(n > 0 && h > 0 && w > 0, "dn_forward: bad shape n=%d h=%d w=%d", n, h, w);
     struct Busy {
@@ -1289,8 +1291,9 @@ static int forward_impl(dn_plan* p, const void* images, int n, int h, int w, flo
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // (inside the guard: dn_set_packed_output refuses to change the stored setting while a call is in progress)
-    const Call call{images, u8, n, h, w, boxes, scores, labels, counts, p->packed_out, reinterpret_cast<unsigned char*>(workspace), heads_only};
-    p->heads_partial[workspace] = !heads_only;
+    DN_REQUIRE(!features_only || !p->profiling, "dn_forward_features: not available between dn_profile_begin and dn_profile_end");
+    const Call call{images, u8, n, h, w, boxes, scores, labels, counts, p->packed_out, reinterpret_cast<unsigned char*>(workspace), heads_only, features_only};
+    p->heads_partial[workspace] = !heads_only || features_only;      // true: the head arrays of this workspace are not (all) written
     const int S = batch_split(p, n);
     if (p->profiling) {
         const size_t stride = p->ops.size() + 6;
@@ -1377,6 +1380,28 @@ extern "C" int dn_forward_heads(dn_plan* plan, const float* images_dev, int n, i
                                 size_t workspace_bytes, void* stream) {
     return forward_impl(plan, images_dev, n, h, w, nullptr, nullptr, nullptr, nullptr, workspace_dev, workspace_bytes, stream,
                         true);
+}
+
+extern "C" int dn_forward_features(dn_plan* plan, const float* images_dev, int n, int h, int w, void* workspace_dev,
+                                   size_t workspace_bytes, void* stream) {
+    return forward_impl(plan, images_dev, n, h, w, nullptr, nullptr, nullptr, nullptr, workspace_dev, workspace_bytes, stream,
+                        true, false, true);
+}
+
+extern "C" int dn_level_features(const dn_plan* p, void* workspace, int n, int level, int chain, void** ptr, int* first_image, int* images) {
+    DN_REQUIRE(p && workspace && n > 0 && ptr, "dn_level_features: bad argument");
+    DN_REQUIRE(level >= 0 && level < p->d.n_levels, "dn_level_features: level %d out of range (%d levels)", level, p->d.n_levels);
+    const int S = batch_split(p, n);
+    DN_REQUIRE(chain >= 0 && chain < S, "dn_level_features: chain %d out of range (a forward of %d images runs as %d)", chain, n, S);
+    const int t = p->d.level_tensor[level];
+    const Layout& L = S == 1 ? get_layout(const_cast<dn_plan*>(p), n) : get_sub_layout(const_cast<dn_plan*>(p), n, S, chain);
+    DN_REQUIRE(L.toff[t] != (size_t)-1, "dn_level_features: level %d is not materialised in the workspace", level);
+    int n0 = 0;
+    for (int q = 0; q < chain; ++q) n0 += sub_count(n, S, q);
+    *ptr = reinterpret_cast<unsigned char*>(workspace) + L.toff[t];
+    if (first_image) *first_image = n0;
+    if (images) *images = S == 1 ? n : sub_count(n, S, chain);
+    return DN_OK;
 }
 
 extern "C" int dn_head_outputs(const dn_plan* p, void* workspace, int n, float** logits, float** reg) {

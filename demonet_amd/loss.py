@@ -8,8 +8,9 @@ SURVEY section 8(f) row 4), and differentiable with respect to both head outputs
 When grad mode is on and `cls_logits` or `bbox_regression` requires grad, the value comes from `dn_ssd_loss_train` (the same launches,
 the same bits) and the returned losses carry a grad_fn whose backward is one HIP launch (`dn_ssd_loss_backward`); only the gradients
 that are needed are computed, and they arrive in the caller's dtype and layout. Otherwise the call is `dn_ssd_loss` as before.
-`anchors` and `targets` are not differentiable; neither is the backward itself (once_differentiable). The gradients stop at the
-head outputs: this repo has no backward through the heads or the backbone.
+`anchors` and `targets` are not differentiable; neither is the backward itself (once_differentiable). These gradients stop
+at the head outputs; `SSD.loss` continues them to the parameters of the model's own SSDLite heads (demonet_amd/headgrad.py). There is no
+backward through the backbone.
 
 `head_outputs` = {'cls_logits': [N, A, K], 'bbox_regression': [N, A, 4]} fp32 CUDA tensors (e.g. `SSD.forward_heads`), `anchors`
 = [A, 4] (or the reference's list of N identical [A, 4] tensors), `targets` = list of {'boxes': [G, 4], 'labels': [G] int64}.

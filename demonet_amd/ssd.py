@@ -134,6 +134,7 @@ class SSD(_Tracked):
         self._graph_mode = None       # set_graph_mode; None: never asked, the library's default (DN_GRAPH) holds
         self._plan_gen = 0            # counts the plans built (a new plan may reuse the old one's address: pipelines compare this)
         self._pipe_refs, self._pipe_chains = 0, None      # open ForwardPipelines of the current plan, and the `chains` they share
+        self._feat_gen = 0            # counts the forwards that wrote this model's workspaces (a head backward checks its features are still there)
         self.eval()
 
     # ------------------------------------------------------------------------------------------------------
@@ -148,22 +149,29 @@ class SSD(_Tracked):
             dev = t.device
         return (hash(tuple(sig)), str(dev), self.score_thresh, self.nms_thresh, self.detections_per_img, self.topk_candidates)
 
-    def _weights_unchanged(self, device) -> bool:
+    def _weights_unchanged(self, device, heads_may_differ: bool = False) -> bool:
         """The per-call form of the test above: True when the plan in hand is still what the current weights lower to. Same criteria
         (tensor identities through the structure epoch, storage addresses, in-place version counters, the post-process settings), walked
-        over a cached flat list."""
+        over a cached flat list. heads_may_differ: only the backbone part of the list is compared -- the training forward takes the
+        features from the plan and computes the heads from the current parameters itself (headgrad.py), so optimizer steps on the heads
+        do not rebuild the plan; the remembered state is left as it is, and the next eval forward sees the change and rebuilds once."""
         c = self._fast_sig
         if c is None or c[0] != _STRUCT_EPOCH[0]:
             return False
-        _, dev, hyper, tensors, ptrs, vers = c
+        _, dev, hyper, tensors, ptrs, vers, n_backbone = c
         if dev != device or hyper != (self.score_thresh, self.nms_thresh, self.detections_per_img, self.topk_candidates):
             return False
+        if heads_may_differ:
+            tensors, ptrs, vers = tensors[:n_backbone], ptrs[:n_backbone], vers[:n_backbone]
         return [t._version for t in tensors] == vers and [t.data_ptr() for t in tensors] == ptrs
 
     def _remember_weights(self, device):
-        tensors = list(self.parameters()) + list(self.buffers())
+        named = list(self.named_parameters()) + list(self.named_buffers())
+        tensors = [t for k, t in named if not k.startswith("head.")]      # the backbone part first, then the head's
+        n_backbone = len(tensors)
+        tensors += [t for k, t in named if k.startswith("head.")]
         self._fast_sig = (_STRUCT_EPOCH[0], device, (self.score_thresh, self.nms_thresh, self.detections_per_img, self.topk_candidates),
-                          tensors, [t.data_ptr() for t in tensors], [t._version for t in tensors])
+                          tensors, [t.data_ptr() for t in tensors], [t._version for t in tensors], n_backbone)
 
     def invalidate(self):
         """Drop the device plan; the next forward lowers the current parameters again. Needed only after weight edits that bypass
@@ -180,11 +188,11 @@ class SSD(_Tracked):
         self.invalidate()
         return super()._apply(fn, *args, **kwargs)
 
-    def _plan(self, device):
+    def _plan(self, device, heads_may_differ: bool = False):
         if device.type != "cuda":
             raise RuntimeError("demonet_amd runs on an MI355X only (images must be on a cuda device); "
                                "there is no CPU fallback path")
-        if self._handle is not None and self._weights_unchanged(device):
+        if self._handle is not None and self._weights_unchanged(device, heads_may_differ):
             return self._handle
         sig = (self._weights_signature(), str(device))
         if self._handle is not None and sig == self._sig:
@@ -274,6 +282,7 @@ class SSD(_Tracked):
         dev = images.device
         stream = torch.cuda.current_stream(dev).cuda_stream
         self._set_packed(packed)
+        self._feat_gen += 1
         # one C call per forward: the argument tuple of (plan, buffers, input address, stream) is built once and reused while none
         # of them changes -- a synchronous caller pays for every microsecond of Python in front of the graph launch
         key = (handle, b["ws"].data_ptr(), src.data_ptr(), stream)
@@ -320,6 +329,7 @@ class SSD(_Tracked):
         b = self._buffers_for(n, h, w, images.device)
         stream = torch.cuda.current_stream(images.device).cuda_stream
         self._set_packed(packed)
+        self._feat_gen += 1
         with torch.cuda.device(images.device):
             _lib.check(_lib.lib().dn_forward_u8(*forward_args(handle, images.data_ptr(), n, h, w, b["outs"], b["ws"], stream)), "dn_forward_u8")
         return b["outs"]
@@ -339,6 +349,7 @@ class SSD(_Tracked):
         b["images"].copy_(images)
         L = _lib.lib()
         stream = torch.cuda.current_stream(images.device).cuda_stream
+        self._feat_gen += 1
         with torch.cuda.device(images.device):
             _lib.check(L.dn_forward_heads(C.c_void_p(handle), C.c_void_p(b["images"].data_ptr()), n, h, w,
                                           C.c_void_p(b["ws"].data_ptr()), b["ws"].numel(), C.c_void_p(stream)), "dn_forward_heads")
@@ -369,13 +380,14 @@ class SSD(_Tracked):
         """The training loss (generalized_ssd.py:210-269 on the matching of :316-330), computed on the GPU by dn_ssd_loss
         (demonet_amd/loss.py). When head_outputs['cls_logits'] or ['bbox_regression'] requires grad, the returned losses are
         differentiable with respect to them (dn_ssd_loss_train / dn_ssd_loss_backward), so any PyTorch head can be trained against
-        this loss; the backward through this model's own fp16 backbone stays out of scope. `anchors` defaults to the model's own
+        this loss -- and this model's own SSDLite heads through SSD.loss, which continues the gradient to their parameters
+        (headgrad.py); the backward through the fp16 backbone stays out of scope. `anchors` defaults to the model's own
         default boxes; `matched_idxs`, which the reference's forward computes and passes in, is recomputed here and, when given,
         checked against."""
         from .loss import ssd_loss
         dev = head_outputs["cls_logits"].device
         if anchors is None:
-            self._plan(dev)
+            self._plan(dev, heads_may_differ=True)      # (the default boxes do not depend on the weights: no rebuild between optimizer steps on the heads)
             anchors = torch.from_numpy(self._lowered.anchors).to(dev)
         losses, matched = ssd_loss(head_outputs, anchors, targets, iou_thresh, (1.0 - positive_fraction) / positive_fraction)
         if matched_idxs is not None:
@@ -384,14 +396,41 @@ class SSD(_Tracked):
                 raise ValueError("compute_loss: matched_idxs differ from the SSDMatcher result for these targets and anchors")
         return losses
 
+    def head_parameters(self) -> "OrderedDict[str, nn.Parameter]":
+        """The parameters of the SSDLite heads (conv weights and biases, BN weight and bias) by the reference's names -- what
+        train_heads() switches and SSD.loss(...).backward() fills. NotImplementedError for the dense 3x3 heads of the VGG models."""
+        from .headgrad import parameter_names
+        named = dict(self.named_parameters())
+        return OrderedDict((k, named[k]) for k in parameter_names(self.graph))
+
+    def train_heads(self, mode: bool = True):
+        """requires_grad of every head parameter (and of nothing else): fine-tuning the heads on the frozen backbone. Default: False
+        for every parameter of the model."""
+        for p in self.head_parameters().values():
+            p.requires_grad_(bool(mode))
+        return self
+
+    def _heads_trainable(self) -> bool:
+        if not any(p.requires_grad for k, p in self.named_parameters() if k.startswith("head.")):
+            return False
+        return any(p.requires_grad for p in self.head_parameters().values())
+
     def loss(self, images: Tensor, targets: List[Dict[str, Tensor]]) -> Dict[str, Tensor]:
         """Backbone + heads (forward_heads) -> compute_loss: the loss values a reference model in train mode would return for this
         batch with the same (eval-mode, BN folded) weights. images: [N,3,H,W] AT THE NETWORK SIZE: the reference's transform also resizes
-        the target boxes with the images (transform.py:93-108), which this entry point does not do -- other sizes raise."""
+        the target boxes with the images (transform.py:93-108), which this entry point does not do -- other sizes raise.
+        When grad mode is on and a head parameter requires grad (train_heads), the returned losses are differentiable with respect to
+        the head parameters: backward() fills .grad of every head parameter that requires it and of nothing else (headgrad.py: features
+        from the plan, the heads from the current fp32 parameters, head BN on its running statistics). Otherwise the call is the plain
+        one: the same launches, the same bits."""
         W, H = self.graph.size
         if tuple(images.shape[-2:]) != (H, W):
             raise ValueError("SSD.loss: images of {}x{} but the network size is {}x{}; resize the images AND the target boxes first "
                              "(the reference's transform does both, transform.py:93-108)".format(images.shape[-2], images.shape[-1], H, W))
+        if torch.is_grad_enabled() and self._heads_trainable():
+            from .headgrad import head_outputs
+            _require_float_batch(images)
+            return self.compute_loss(targets, head_outputs(self, images))
         logits, reg = self.forward_heads(images)
         return self.compute_loss(targets, {"cls_logits": logits, "bbox_regression": reg})
 
@@ -399,8 +438,13 @@ class SSD(_Tracked):
         if self.training:
             if targets is None:
                 raise ValueError("In training mode, targets should be passed")     # generalized_ssd.py:273-274
-            raise NotImplementedError("demonet_amd implements the inference path only (SURVEY.md section 8); the loss VALUE of a batch "
-                                      "is available through SSD.loss(images, targets) / compute_loss (differentiable w.r.t. the head outputs it is given)")
+            if self._heads_trainable():                                             # generalized_ssd.py:271-349, training branch
+                if not isinstance(images, Tensor):
+                    images = torch.stack(list(images))
+                return self.loss(images, targets)
+            raise NotImplementedError("demonet_amd trains the SSDLite heads on the frozen backbone only, and no head parameter of this model requires "
+                                      "grad: call train_heads() first (VGG models: not covered). The loss VALUE of a batch is available through "
+                                      "SSD.loss(images, targets) / compute_loss (differentiable w.r.t. the head outputs it is given)")
         legacy = isinstance(images, Tensor) and images.dim() == 4                   # hub call form model(x[1,3,S,S], shapes)
         if legacy:
             images = list(images.unbind(0))

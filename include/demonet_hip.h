@@ -116,6 +116,18 @@ DN_API int dn_head_outputs(const dn_plan* plan, void* workspace_dev, int n, floa
 /* Device address/size of an intermediate tensor inside the workspace (parity tests on feature maps). */
 DN_API int dn_tensor_ptr(const dn_plan* plan, void* workspace_dev, int n, int tensor_id, void** ptr, size_t* bytes);
 
+/* The level feature maps of the last forward on this workspace, for callers that continue from them (the head backward below).
+ * A forward of n images runs as dn_batch_split(plan, n) sub-batch chains, each with an arena of its own, so a level tensor is one
+ * contiguous [images][h][w][c] fp16 NHWC piece PER CHAIN: *ptr = the piece of chain `chain` (0 .. dn_batch_split - 1), *first_image =
+ * index of its first image in the batch, *images = its image count (either may be NULL). The pieces stay valid until the next forward
+ * on the workspace. dn_tensor_ptr serves the single-chain case only. */
+DN_API int dn_level_features(const dn_plan* plan, void* workspace_dev, int n, int level, int chain, void** ptr, int* first_image, int* images);
+/* Backbone only: dn_forward_heads without its head launches -- the same launch list, stopped in front of them; ends with the level
+ * tensors (dn_level_features) complete. The head arrays of the workspace are not written (dn_head_outputs refuses). For a training
+ * step that computes the heads from its own, current weights. Not available while profiling. */
+DN_API int dn_forward_features(dn_plan* plan, const float* images_dev, int n, int h, int w,
+                               void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Post-process only, replacing SSD.postprocess_detections (generalized_ssd.py:351-397) + transform.postprocess:
  * softmax -> decode (BoxCoder weights 10,10,5,5) -> clip -> per-class score>thr & top-k -> hard NMS (IoU > thr)
  * -> global top-D by score.  kept_anchor_dev (optional, may be NULL): [n][D] int32 anchor index per detection.
@@ -199,7 +211,7 @@ DN_API int dn_ssd_loss(const float* cls_logits_dev, const float* bbox_regression
                        int n, int num_anchors, int num_classes, int gmax, float iou_thresh, float neg_to_pos_ratio,
                        int64_t* matched_idxs_dev, float* losses_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
-/* The same loss with its gradient for both head outputs (the gradients stop there: no backward through the heads or the backbone).
+/* The same loss with its gradient for both head outputs (dn_lite_head_backward continues to the SSDLite head parameters; no backward through the backbone).
  * dn_ssd_loss_train = dn_ssd_loss (the same launches: losses_dev and matched_idxs_dev are bit-identical to it) that also keeps, in
  * state_dev (dn_ssd_loss_state_bytes(n, A) bytes, 16-byte aligned, the caller's until the backward has run), what the backward needs:
  * the matched index, the weight w in {0, 1, 2} of every anchor's cross entropy = (label > 0) + (mined negative), and
@@ -220,6 +232,27 @@ DN_API int dn_ssd_loss_backward(const float* cls_logits_dev, const float* bbox_r
                                 const float* gt_boxes_dev, const int64_t* gt_labels_dev, const void* state_dev, size_t state_bytes,
                                 const float* grad_losses_dev, int n, int num_anchors, int num_classes, int gmax,
                                 float* grad_cls_logits_dev, float* grad_bbox_regression_dev, void* stream);
+
+/* Backward through one SSDLite head of one pyramid level (csrc/headgrad.hip): the gradients of the FOLDED head parameters, given the
+ * gradient of the head output. Differentiates  depthwise 3x3 + BN + ReLU6 -> 1x1 conv with bias  (ssd_mobilenetv3.py:27-36; the V2
+ * hub model's MultiBoxLiteHead, box_head.py:24-56, whose last level is a bare 1x1: wd == NULL, h = x, only g_w1 and g_b1 are
+ * written and bd, g_wd, g_bd may be NULL).
+ * x [n][h][w][c] fp16 NHWC (the level's feature map, e.g. dn_tensor_ptr), wd [9][c] fp16, bd [c] fp32, w1 [cout][c] fp16: the
+ * folded weights the forward used. dy: fp32 gradient of the head output, read in place from the [n][A][K] / [n][A][4] gradient
+ * tensor: the row of pixel p of image i is dy + i * dy_img_stride + p * cout (pass the tensor's address plus the level's anchor
+ * offset times K or 4, and A * K or A * 4 as the stride), exactly as dn_pointwise_conv(out_fp32 = 1) addresses the forward's output.
+ *   z = wd (*) x + bd (recomputed, fp32),  h = fp16(min(max(z, 0), 6)),
+ *   g_b1[o] = sum_p dy[p][o],  g_w1[o][c] = sum_p dy[p][o] h[p][c],  dz = (dy w1) where 0 < z < 6,
+ *   g_bd[c] = sum_p dz[p][c],  g_wd[t][c] = sum_p dz[p][c] x[p + t][c]  (nine taps, zero padding).
+ * All four outputs fp32, every element written. The two contractions run on the fp16 matrix cores with dy scaled by a power of
+ * two chosen on the device from max|dy| (no host synchronisation; gradients far below fp16's range keep their bits). Deterministic:
+ * partial sums meet in a fixed order. Asynchronous on `stream`. x, wd, w1 and the workspace 16-byte aligned.
+ * Invalid sizes or pointers: DN_E_INVALID; c % 8 != 0 or cout > 6 * DN_MAX_CLASSES: DN_E_UNSUPPORTED; workspace too small: DN_E_WORKSPACE.
+ * dn_lite_head_backward_workspace_bytes: `depthwise` = 0 for a level without a depthwise stage; 0 for sizes the call rejects. */
+DN_API size_t dn_lite_head_backward_workspace_bytes(int n, int h, int w, int c, int cout, int depthwise);
+DN_API int dn_lite_head_backward(const void* x_dev, const void* wd_dev, const float* bd_dev, const void* w1_dev, const float* dy_dev,
+                                 int64_t dy_img_stride, int n, int h, int w, int c, int cout, float* g_wd_dev, float* g_bd_dev,
+                                 float* g_w1_dev, float* g_b1_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
