@@ -51,7 +51,7 @@ def build_stamps(verbose=True):
 
 def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(os.path.dirname(HERE), "include", "demonet_hip.h"),
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "choice.h"), os.path.join(os.path.dirname(HERE), "include", "demonet_hip.h"),
                os.path.join(os.path.dirname(HERE), "include", "demonet_hip_debug.h")]
     objs = []
     procs = []

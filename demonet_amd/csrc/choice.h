@@ -1,0 +1,319 @@
+// Which kernel a 1x1 convolution, a dense convolution or a grouped head launch runs on: ONE pure function per family (no HIP call, no label, argument
+// untouched; knobs read through dn_knob at the call -- INTEGRATION.md: kernel-choice knobs at every launch). The launchers validate, ask here and switch from
+// the answer to the template instantiation; the plan-time predicates ask the same functions about a shape. The order of the rules in a function is their
+// precedence, with the measurement that justifies a rule next to it; capability tests (*_shape, *_supported) stand in front of the function that uses them.
+#pragma once
+#include "common.h"
+
+struct PwChoice {
+    enum Kernel {
+        NONE,                                               // no kernel of the family takes the problem
+        AS_POINTWISE,                                       // conv_choose: a dense 1x1 that the 1x1 family serves -- pw_choose decides, on conv_1x1_as_pw(a)
+        PW_WSTAT, PW_STREAM, PW_DIRECT,                     // pwdirect.hip: pw_wstat_kernel<KS1 = k, RT = t>, pw_stream_kernel<KSF = k, PX = t>, pw_direct_kernel<KSF = k, TC = t>
+        PW_XS, PW_TILE, PW_GROUP,                           // pointwise.hip: pw_xs_kernel<32>, pw_kernel / pw_group_kernel<bp, bc, .., conv, bk, pf, sef, fk>
+        CONV_PATCH, CONV_PATCH_RESIDENT, CONV_HALO, CONV_GLDS   // convbig.hip; conv_halo_kernel<3, TP, TC, head> by halo: 1 = 256 px x 256 ch, 2 = 512 x 128, 3 = 256 x 128
+    };
+    Kernel kernel = NONE;
+    int bp = 0, bc = 0, bk = 32, pf = 1;      // workgroup tile (pixels x channels), K per stage, stages requested ahead
+    bool conv = false, sef = false, fk = false;   // implicit-GEMM body; squeeze-excitation in the prologue; the bound-test-free K loop
+    int k = 0, t = 0, halo = 0;
+    bool head = false, pool = false;          // fp32 head form (takes the rider w_b); writes the 2 x 2 max-pooled map (pool_out)
+};
+
+// ---- workgroup thresholds. Tile choice of the staged kernels: these GEMMs are latency/HBM-bound, not MFMA-bound, so what matters is (a) enough
+// workgroups to fill 256 CUs several times over and (b) not re-reading x for many channel tiles. Prefer the largest tile that still gives
+// >= ~1500 workgroups, else fall back to smaller tiles.
+constexpr long PW_FILL_WGS = 1500;
+constexpr long PW_64x128_MIN_WGS = 600;
+constexpr long CONV_128x128_MIN_WGS = 300;      // min workgroups for the 128x128 tile of the MFMA-bound dense convs (measured on the VGG models)
+constexpr long CONV_RING_MAX_WGS = 512;         // below: a small dense conv, latency-bound (conv_choose)
+constexpr long CONV_BIG_MIN_WGS = 40;           // 256 x 256 tiles. Measured on both VGG models: 40 < 90 < 200; the sub-batch chains fill the chip together
+constexpr long HEAD_512x128_MIN_WGS = 128;      // half the chip in 512-pixel tiles
+constexpr long GROUP_RING_MAX_WGS = 256;        // (in 128 x 128 tiles) below: a small-level dense head group, latency-bound (pw_group_choose)
+constexpr int PW_DIRECT_TC2_MIN_COUT = 400;
+constexpr int CONV_BIG_TILE = 256, CONV_GLDS_K = 64;      // conv_glds_kernel: tile edge and K per stage (convbig.hip asserts its own constants against these)
+
+inline long pw_wgs(const PwArgs& a, int bp, int bc) { return (long)dn_cdiv(a.m, bp) * dn_cdiv(a.cout, bc); }
+
+// pw_kernel on 32-deep double-buffered K staging (measured and dropped: a single exact-K stage for K <= 128 -- no load/compute overlap, slower; 64-deep double
+// buffer -- lost to occupancy), or (ring) with the stages requested 4 ahead through a register ring
+inline PwChoice pw_tile(const PwArgs& a, bool conv, int bp, int bc, bool ring = false, bool sef = false) {
+    PwChoice c;
+    c.kernel = PwChoice::PW_TILE; c.bp = bp; c.bc = bc; c.conv = conv; c.pf = ring ? 4 : 1; c.sef = sef;
+    // MFMA-bound dense convolutions (VGG): 64-deep stages halve the barriers per MFMA; the tile is register-limited to two
+    // workgroups per CU either way, and 2 x 74 KB of LDS fit
+    if (conv && !ring && bp == 128 && bc == 128 && a.cv_cin % 64 == 0) c.bk = 64;
+    // the bound-test-free K loop (pw_body FK): whole 32-deep stages, no SE-scaled staging, 32-bit byte offsets
+    c.fk = ring && !conv && !sef && dn_knob("DN_PW_FASTK", 1) && a.cin % c.bk == 0 && (!a.se || a.hw >= bp) && !(a.act >> 8) && (size_t)a.m * a.cin < (1u << 30) &&
+           (size_t)a.cout * a.cin < (1u << 30);
+    return c;
+}
+// the last rules of pw_choose and conv_choose: the wide tiles by fill
+inline PwChoice pw_tile_wide(const PwArgs& a, bool conv) {
+    if (pw_wgs(a, 128, 128) >= (conv ? CONV_128x128_MIN_WGS : PW_FILL_WGS)) return pw_tile(a, conv, 128, 128);
+    if ((pw_wgs(a, 128, 64) >= PW_FILL_WGS || a.cout % 128 > 64 || a.cout % 128 == 0) && pw_wgs(a, 64, 128) >= PW_64x128_MIN_WGS) return pw_tile(a, conv, 64, 128);
+    return pw_tile(a, conv, 64, 64);
+}
+
+// ================================================================ (a) one 1x1 convolution
+// register-direct schedule for short reductions (pwdirect.hip)
+inline bool pw_direct_supported(const PwArgs& a) {
+    // squeeze-excitation scaled inputs: only where a 32-row tile lies inside one image (the 40 x 40 maps) and the reduction is short
+    if (a.se && !(a.hw % 32 == 0 && a.cin <= 128)) return false;
+    return dn_knob("DN_PW_DIRECT", 1) != 0 && a.cv_k == 1 && !a.out_fp32 && !a.sef_part && !a.w_b && a.cin % 8 == 0 && a.cin >= 8 &&
+           a.cin <= 256 && a.cout % 8 == 0 && a.cout >= 8 && !(a.act >> 8) && a.out_img_stride == 0 && a.out_base == 0;
+}
+inline bool pw_wstat_supported(const PwArgs& a) {
+    return dn_knob("DN_PW_WSTAT", 1) != 0 && a.wfrag && !a.se && !a.residual && a.cin >= 16 && a.cin <= 128 && a.cin % 8 == 0 && a.m >= 3200 &&
+           (long)a.m * a.cout * 2 < 0x7fffffffL && a.cout >= 64;
+}
+// the squeeze-excitation of a projection can be computed in the projection kernel's prologue (SEF variant of the 64 x 64 tile)
+inline bool pw_sef_supported(const PwArgs& a) {
+    return dn_knob("DN_SE_FOLD", 1) != 0 && !a.se && a.cin % 8 == 0 && a.sef_sq <= 32 && a.hw >= 64;
+}
+
+inline PwChoice pw_choose(const PwArgs& a) {
+    PwChoice c;
+    if (pw_direct_supported(a)) {
+        // the expansions (short reduction, wide output, no scale, no residual): weight-stationary waves over LDS-DMA'd pixel tiles (round 6)
+        if (pw_wstat_supported(a)) {
+            c.kernel = PwChoice::PW_WSTAT;
+            c.k = a.cin / 16 + 1;
+            const int ctiles = dn_cdiv(a.cout, 32);
+            // tiles per run: as many as 96 registers of A fragments allow, least padding of the last run first
+            int waste = 1 << 30;
+            c.t = 2;
+            for (int rt = 4; rt >= 2; --rt) {
+                if (c.k * rt > 24) continue;
+                const int w = dn_cdiv(ctiles, rt) * rt - ctiles;
+                if (w < waste) { waste = w; c.t = rt; }
+            }
+            return c;
+        }
+        const int ctiles = dn_cdiv(a.cout, 32);
+        const int ksf = a.cin >> 4;
+        c.k = ksf;
+        // wide expansions with enough rows: the streaming variant (pw_stream_kernel) -- channel runs sized so that all waves are resident at once
+        if (dn_knob("DN_PW_STREAM", 1) && !a.se && !a.residual && ksf >= 4 && ksf <= 8 && ctiles >= 12 && a.m >= 12800) {
+            c.kernel = PwChoice::PW_STREAM;
+            c.t = 2;                        // 32-pixel tiles per wave
+            return c;
+        }
+        // One 32-channel tile per wave (TC = 1) on the narrow layers: these launches are latency-bound, and twice the waves with half the
+        // registers overlap their single memory round trip better. Wide expansions (cout >= PW_DIRECT_TC2_MIN_COUT, short reductions) take two
+        // tiles per wave: every wave re-reads its x rows once per channel tile, and at 21 tiles (112 -> 672) that is most of the traffic
+        // (measured: threshold 400 -> batch 64 1.115 -> 1.107 ms, batch 32 0.79 -> 0.77 ms; 200 and 600 in between).
+        c.kernel = PwChoice::PW_DIRECT;
+        c.t = (ksf <= 8 && a.cout >= PW_DIRECT_TC2_MIN_COUT) ? 2 : 1;
+        return c;
+    }
+    if (dn_knob("DN_PW_XS", 1) && !a.sef_part && a.wfrag && a.cin % 16 == 0 && a.cin <= 1024 && a.cout <= 160 && !(a.act >> 8) &&      // (K % 16 == 8: measured slower than the tiled kernel)
+        ((a.cin >= 64 && a.m <= 8192) || (a.cin >= 160 && a.m <= 16384))) {
+        // measured (tools/tune_pw.py): the strip kernel wins where the tiled kernel cannot fill the chip -- M <= ~8k rows, or
+        // M <= ~16k rows when K is long (the tiled kernel pays one exposed round trip per 32-deep K stage)
+        c.kernel = PwChoice::PW_XS;
+        return c;
+    }
+    // 1x1 convs with a thin side (cin < 256 or cout < 128) are HBM/latency-bound: tools/tune_pw.py over every layer shape
+    // of the model shows the small tiles (most workgroups, fewest registers: 64 VGPRs -> 8 waves/SIMD) winning or tying
+    // everywhere, 128x32 when there is a single channel tile. The big tiles only pay off for MFMA-bound shapes.
+    if (a.cin < 256 || a.cout < 128) {
+        if (a.cin > 32) {
+            // the register ring on both measured cases: 2..4 K stages (cin <= 128), all loads up front; long K on a thin layer (cin > 128), loads 4 stages ahead
+            if (a.sef_part && a.cin <= 128 && pw_sef_supported(a)) return pw_tile(a, false, 64, 64, true, true);     // squeeze-excitation folded in
+            return a.cout <= 32 ? pw_tile(a, false, 128, 32, true) : pw_tile(a, false, 64, 64, true);
+        }
+        return a.cout <= 32 ? pw_tile(a, false, 128, 32) : pw_tile(a, false, 64, 64);
+    }
+    // a 1x1 layer with few workgroups and a long K (the first extras layer: 480 -> 256 on 10 x 10) is a chain of exposed round trips with the plain
+    // double buffer: stages requested 4 ahead on the bound-test-free loop. Measured (round 3): the launch 18.8 -> 14 us, one forward at a time -5 us,
+    // with three forwards in flight 0.2 - 0.3 % slower in three of three pairs: opt-in
+    // (cin >= 256 and cout >= 128 here)
+    if (dn_knob("DN_PW_LONGK_PF", 0) && a.cin % 32 == 0 && pw_wgs(a, 64, 64) < PW_FILL_WGS) return pw_tile(a, false, 64, 64, true);
+    return pw_tile_wide(a, false);
+}
+
+// ================================================================ (b) one dense convolution
+// the 1x1 problem that a dense 1x1 / stride 1 / pad 0 conv with fp16 output is
+inline PwArgs conv_1x1_as_pw(const PwArgs& a) {
+    PwArgs b;
+    b.x = a.x; b.w = a.w; b.bias = a.bias; b.residual = nullptr; b.se = nullptr; b.out = a.out;
+    b.hw = a.hw; b.m = a.m; b.cin = a.cv_cin; b.cout = a.cout; b.act = a.act; b.out_fp32 = 0; b.out_img_stride = 0; b.out_base = 0;
+    b.xq = a.xq;
+    return b;
+}
+// the one-image 3 x 3 "same" conv that a plan-time (cin, cout, h, w) question is about
+inline PwArgs conv3x3_query(int cin, int cout, int h, int w) {
+    static const half_t dummy_zero[8] = {};
+    PwArgs a{};
+    a.cv_k = 3; a.cv_stride = 1; a.cv_pad = 1; a.cv_dil = 1; a.cv_h = a.cv_ho = h; a.cv_w = a.cv_wo = w; a.cv_cin = cin;
+    a.zeros = dummy_zero; a.residual = nullptr; a.se = nullptr; a.out_fp32 = 0;
+    a.hw = h * w; a.m = a.hw; a.cin = 9 * cin; a.cout = cout;
+    return a;
+}
+
+// conv_patch_kernel / conv_patch_resident_kernel: 3 x 3 "same", 64 or 128 input channels
+inline bool patch_shape(const PwArgs& a) {
+    return a.zeros && !a.out_fp32 && !a.residual && !a.se && a.cv_k == 3 && a.cv_stride == 1 && a.cv_pad == 1 && a.cv_dil == 1 &&
+           a.cv_ho == a.cv_h && a.cv_wo == a.cv_w && a.cv_cin % 64 == 0 && a.cv_cin <= 128 && a.cout % 64 == 0 && a.m / a.hw <= 65535;
+}
+inline bool patch_resident_shape(const PwArgs& a) {
+    const long out_bytes = (long)(a.m / a.hw) * (a.pool_out ? (a.cv_h >> 1) * (a.cv_w >> 1) : a.cv_h * a.cv_w) * a.cout * 2;
+    return a.cv_cin == 64 && a.act == DN_ACT_RELU && out_bytes < 0xFFFFFFF0L && (long)a.cv_h * a.cv_w * 128 < (1L << 31) && dn_knob("DN_PATCH_RESIDENT", 1) != 0;
+}
+// conv_halo_kernel: the run-staged tiles
+constexpr int halo_run_rows(int tp, int tc) { return tc == 4 ? 704 : tp == 8 ? 832 : 960; }      // rows of a staged run (pixel tile + halo on both sides), upper bound
+inline bool halo_shape(const PwArgs& a) {
+    const int halo = dn_knob("DN_CONV_HALO", 1);
+    return halo && a.zeros && a.cv_k == 3 && a.cv_stride == 1 && a.cv_pad == a.cv_dil && a.cv_ho == a.cv_h && a.cv_wo == a.cv_w &&
+           a.cv_cin % 64 == 0 && (long)a.m * a.cv_cin * 2 < (1L << 31) && (long)(a.cout + a.cout_b) * a.cin * 2 < (1L << 32);
+}
+inline int halo_rows(const PwArgs& a) { return 2 * (a.cv_pad * a.cv_w + a.cv_pad); }
+// which tile a fp16-output 3x3 stride-1 conv runs on: 0 none, 1 = 256 x 256, 2 = 512 x 128, 3 = 256 x 128
+inline int halo_variant(const PwArgs& a) {
+    if (a.out_fp32 || a.residual || a.se || !halo_shape(a)) return 0;
+    const int hr = halo_rows(a);
+    if (a.cout % 256 == 0 && 256 + hr <= halo_run_rows(4, 4)) return 1;
+    if (a.cout % 128 == 0 && a.cv_cin >= 128 && 512 + hr <= halo_run_rows(8, 2)) return 2;
+    if (a.cout % 128 == 0 && a.cv_cin >= 128 && 256 + hr <= halo_run_rows(4, 2)) return 3;      // (one 64-channel iteration: measured level with the 128x128 tile)
+    // (a 256 x 64 tile for the 64-channel layer conv1_2: 330 vs 388 TFLOP/s for the 128 x 64 tile of pointwise.hip -- four MFMAs per K
+    // step cannot cover the fragment masks and reads)
+    return 0;
+}
+// ... with the max-pool epilogue (conv3_3 of ssd512: 256 channels on 128 x 128), asked of ONE image: the tile must be whole row pairs of one
+// image (256 % 2W == 0, H W % 256 == 0)
+inline bool halo_pool_shape(const PwArgs& one) {
+    return !(one.cv_h & 1) && !(one.cv_w & 1) && halo_variant(one) == 1 && 256 % (2 * one.cv_w) == 0 && one.hw % 256 == 0;
+}
+inline bool conv_glds_shape(const PwArgs& a) {
+    return a.zeros && a.cv_cin % CONV_GLDS_K == 0 && a.cout % CONV_BIG_TILE == 0 && !a.out_fp32 && !a.residual && !a.se && a.cv_k * a.cv_k <= 32 && a.cin >= 2 * CONV_GLDS_K &&
+           (long)a.m / a.hw * a.cv_h * a.cv_w * a.cv_cin * 2 < (1L << 31) && (long)a.cout * a.cin * 2 < (1L << 32);
+}
+
+enum ConvUse {
+    CONV_PLAIN,     // launch_conv
+    CONV_POOLED,    // launch_conv_pool: MaxPool2d(2, 2) in the epilogue (a.pool_out)
+    CONV_HEAD       // launch_conv_head_big: a dense fp32 head on the run-staged tiles, with or without the rider (a.w_b); NONE: the group launch takes it
+};
+
+inline PwChoice conv_choose(const PwArgs& a, ConvUse use) {
+    PwChoice c;
+    c.conv = true;
+    if (use == CONV_HEAD) {
+        // Dense 3x3 heads with fp32 outputs (SSDHead, generalized_ssd.py:77-92) on the run-staged tiles; channel tiles beyond cout compute on the last
+        // weight row and are not stored. The class + box channels of a level (380 / 570 for 91 classes) fill 74 % of two / three 256-channel tiles but
+        // 99 % / 89 % of three / five 128-channel tiles, and the 512 x 128 run tile runs level with the 256 x 256 one per FLOP (conv3 .. conv5 of
+        // ssd512_vgg16: 1140-1330 vs 1150-1320 TFLOP/s): the idle channels were a quarter of the head launches' time. A level too small for half the
+        // chip in 512-pixel tiles (the 16 x 16 level of ssd512 at batch 32: 80 workgroups) takes 256 x 128 tiles -- twice the workgroups at half the
+        // work each.
+        if (!dn_knob("DN_CONV_HEAD_BIG", 1) || !a.out_fp32 || a.residual || a.se || !halo_shape(a) || (a.cout & 1)) return c;
+        c.head = true;
+        const int hr = halo_rows(a), nc = a.cout + a.cout_b;
+        const int c256 = dn_cdiv(nc, 256), c128 = dn_cdiv(nc, 128);
+        const long p256 = dn_cdiv(a.m, 256), p512 = dn_cdiv(a.m, 512);
+        if (dn_knob("DN_CONV_HEAD_NARROW", 1) && c128 * 128 < c256 * 256 && a.cv_cin >= 128) {
+            if (512 + hr <= halo_run_rows(8, 2) && p512 * c128 >= HEAD_512x128_MIN_WGS) c.halo = 2;
+            else if (256 + hr <= halo_run_rows(4, 2) && p256 * c128 >= 2 * CONV_BIG_MIN_WGS) c.halo = 3;      // (40 workgroups of the 8 x 8 level: slower than the group launch)
+        }
+        const int tiles = dn_cdiv(a.cout, 256);
+        if (!c.halo && 256 + hr <= halo_run_rows(4, 4) && a.cout * 10 >= tiles * 256 * 6 && p256 * tiles >= CONV_BIG_MIN_WGS) c.halo = 1;      // at most 40 % of the channel tiles idle
+        if (c.halo) c.kernel = PwChoice::CONV_HALO;
+        return c;
+    }
+    const bool patch = patch_shape(a);
+    const PwChoice::Kernel patch_kernel = patch_resident_shape(a) ? PwChoice::CONV_PATCH_RESIDENT : PwChoice::CONV_PATCH;
+    if (use == CONV_POOLED) {
+        // By geometry alone, and of ONE image (the launcher walks a batch beyond the run-staged tile's 2 GB in image ranges). This is the one place where
+        // launch and plan deliberately differ: DN_CONV_BIG / DN_CONV_POOL / DN_CONV_HALO_POOL decide at dn_create (conv_patch_pool_ok,
+        // conv_halo_pool_ok), the launch only checks the geometry, so a knob flipped between dn_create and dn_forward cannot strand a fused pair.
+        // Nor may a.out steer the choice: the patch kernel never writes the full-resolution map (a pair whose map has other readers is only fused
+        // when the run-staged tile takes it: plan.hip), and a.out is non-null for EVERY tensor with DN_WS_REUSE=0.
+        PwArgs one = a;
+        one.m = a.hw;
+        c.pool = true;
+        // 64 input channels: always the patch kernel
+        if (halo_pool_shape(one) && !(patch && a.cv_cin <= 64) && pw_wgs(one, 256, 256) >= CONV_BIG_MIN_WGS) { c.kernel = PwChoice::CONV_HALO; c.halo = 1; }
+        else if (patch) c.kernel = patch_kernel;
+        return c;
+    }
+    // the 256 x 256-tile kernels (convbig.hip), where one of them takes the shape and the launch has enough of their workgroups
+    const int hv = halo_variant(a);
+    const bool big = dn_knob("DN_CONV_BIG", 1) && (hv || patch || conv_glds_shape(a)) && pw_wgs(a, 256, 256) >= CONV_BIG_MIN_WGS;
+    // a 1x1 dense conv IS a pointwise conv: unless it is big enough for the 256 x 256-tile kernel, the pointwise path serves it
+    // (register-direct kernel up to cin = 256, 4-stage prefetch ring beyond; the implicit-GEMM body walks it one exposed stage at a time)
+    if (!big && a.cv_k == 1 && a.cv_stride == 1 && a.cv_pad == 0 && !a.out_fp32) { c.kernel = PwChoice::AS_POINTWISE; return c; }
+    if (big) {
+        // 64 input channels: always the patch kernel; 128: where the run kernel would need its 256 x 128 tile (maps wider than 159; measured:
+        // conv2_2 of ssd512 882 vs 568 TFLOP/s, while the 512 x 128 run tile of the 150-wide map keeps the faster step)
+        if (patch && (a.cv_cin <= 64 || hv == 0 || hv == 3)) { c.kernel = patch_kernel; return c; }
+        c.kernel = hv ? PwChoice::CONV_HALO : PwChoice::CONV_GLDS;
+        c.halo = hv;
+        return c;
+    }
+    if (a.cout <= 32) return pw_wgs(a, 256, 32) >= PW_FILL_WGS ? pw_tile(a, true, 256, 32) : pw_tile(a, true, 128, 32);
+    if (a.cout <= 64) return pw_wgs(a, 128, 64) >= PW_FILL_WGS ? pw_tile(a, true, 128, 64) : pw_tile(a, true, 64, 64);
+    // small dense convs (the extras of the VGG models: <= 16 x 16 maps, K = 9 cin up to 4608): a few workgroups walking 70 - 140
+    // K stages, each an exposed memory round trip with the plain double buffer (60 - 130 us per layer for < 1 us of MFMA work):
+    // request the stages 4 ahead through the register ring of the short-K pointwise variant
+    if (pw_wgs(a, 64, 64) < CONV_RING_MAX_WGS) return pw_tile(a, true, 64, 64, true);
+    return pw_tile_wide(a, true);
+}
+
+// ================================================================ (c) a grouped head launch
+// All problems are of the same kind (pointwise or implicit-GEMM conv); the tile is chosen for the widest one. Stages requested ahead: head 1x1
+// convs have long K (21 stages at level 0), loads run 3 stages ahead; the dense-conv heads of the VGG models are MFMA-bound at 184 VGPRs and keep
+// the plain double buffer -- except the small levels.
+inline PwChoice pw_group_choose(const PwArgs* arr, int count, bool conv) {
+    int maxc = 0;
+    long wg128 = 0;
+    bool all64 = true;
+    for (int i = 0; i < count; ++i) {
+        if (arr[i].cout > maxc) maxc = arr[i].cout;
+        wg128 += pw_wgs(arr[i], 128, 128);
+        all64 &= arr[i].cv_cin % 64 == 0;
+    }
+    PwChoice c;
+    c.kernel = PwChoice::PW_GROUP; c.conv = conv; c.pf = conv ? 1 : 3;
+    auto tile = [&](int bp, int bc) { c.bp = bp; c.bc = bc; };
+    if (maxc <= 32) { tile(128, 32); if (conv && wg128 < GROUP_RING_MAX_WGS) c.pf = 3; }
+    else if (maxc <= 64) tile(64, 64);
+    else if (wg128 >= PW_FILL_WGS) {
+        tile(128, 128);
+        // MFMA-bound dense-conv heads: 64-deep stages as in pw_tile (half the barriers per MFMA)
+        if (conv && all64) c.bk = 64;
+        if (!conv) {
+            // 96-wide channel tiles (a wave = 32 pixels x 96 channels) where they pad less: the 546 class channels of the SSDLite heads are
+            // 6 x 96 = 576 columns instead of 5 x 128 = 640 -- the head launch is the longest full-chip launch of a forward (batch 64, three
+            // forwards in flight: 0.789 -> 0.775 ms; 128 x 192 tiles 0.808, 64 x 192 level)
+            double c96 = 0, c128 = 0;
+            for (int i = 0; i < count; ++i) {
+                c96 += (double)arr[i].m * dn_cdiv(arr[i].cout, 96) * 96;
+                c128 += (double)arr[i].m * dn_cdiv(arr[i].cout, 128) * 128;
+            }
+            if (c96 <= 0.95 * c128) tile(128, 96);
+        }
+    } else {
+        tile(64, 128);
+        // the dense heads of the small levels (a few dozen workgroups, 72 - 144 K stages): latency-bound, stages requested 3 ahead
+        if (conv && wg128 < GROUP_RING_MAX_WGS) c.pf = 3;
+    }
+    if (!conv) {
+        // every problem on the bound-test-free K loop (whole 32-deep stages, no SE-scaled staging, 32-bit byte offsets): the instantiation that holds nothing else
+        c.fk = dn_knob("DN_PW_FASTK", 1) != 0;
+        for (int i = 0; i < count; ++i)
+            c.fk &= arr[i].cin % c.bk == 0 && !arr[i].se && !(arr[i].act >> 8) && (size_t)arr[i].m * arr[i].cin < (1u << 30) && (size_t)arr[i].cout * arr[i].cin < (1u << 30);
+    }
+    return c;
+}
+
+// ================================================================ a request that the chosen kernel does not implement is an error, not a launch
+inline int pw_check_honoured(const PwArgs& a, const PwChoice& c, const char* who) {
+    const char* field = (a.sef_part && !c.sef) ? "sef_part" : (a.w_b && !c.head) ? "w_b" : (a.pool_out && !c.pool) ? "pool_out" : nullptr;
+    if (!field) return DN_OK;
+    dn_set_error("%s: no kernel implements %s for cin=%d cout=%d on %d rows of %d per image (k=%d)", who, field, a.cv_k > 1 ? a.cv_cin : a.cin, a.cout, a.m, a.hw, a.cv_k);
+    return DN_E_UNSUPPORTED;
+}
+
+// the kernels of the other two files, behind their part of the switch
+int launch_pw_direct(const PwArgs& a, const PwChoice& c, hipStream_t s);      // PW_WSTAT, PW_STREAM, PW_DIRECT (pwdirect.hip)
+int launch_conv_big(const PwArgs& a, const PwChoice& c, hipStream_t s);       // CONV_PATCH, CONV_PATCH_RESIDENT, CONV_HALO, CONV_GLDS (convbig.hip)

@@ -171,7 +171,7 @@ struct PwArgs {
     int cv_k = 1, cv_stride = 1, cv_pad = 0, cv_dil = 1, cv_h = 0, cv_w = 0, cv_ho = 0, cv_wo = 0, cv_cin = 0;
     FastDiv fd_cin32{1, 0}, fd_k{1, 0};     // conv_to_pw: (k0 / 32) / (cv_cin / 32) and tap / cv_k without a hardware division per K stage
     const half_t* zeros = nullptr;   // optional: >= 16 zero bytes on the device (dense convs)
-    int cv_plain_order = 0;          // dev knob DN_CONV_PLAIN_ORDER: conv_halo_kernel tiles in plain (x, y) order instead of XCD-grouped
+    int cv_plain_order = 0;          // always 0 (nothing sets it): 1 = conv_halo_kernel walks its tiles in plain (x, y) order instead of XCD-grouped
     // optional second head on the same input (convbig.hip, head kernel): output channels [cout, cout + cout2) use these
     const half_t* w_b = nullptr; const float* bias_b = nullptr; void* out_b = nullptr;
     int cout_b = 0; long out_b_img_stride = 0, out_b_base = 0;
@@ -195,21 +195,17 @@ struct PwArgs {
 };
 constexpr int DN_PP_HSHIFT = 19;      // score histogram: float bits 30..19 (8 exponent + 4 mantissa bits)
 constexpr int DN_PP_HBINS = 256;      // bins kept: the top 256 (scores down to 2^-16); anything lower shares bin 0
+// 1x1 and dense convolutions (pointwise.hip, pwdirect.hip, convbig.hip). Which kernel a launch takes is decided by the choice functions of choice.h
+// and nowhere else; the plan-time predicates below are questions to those functions.
 int launch_pointwise(const PwArgs& a, hipStream_t s);
-// register-direct schedule for short reductions (pwdirect.hip)
-bool pw_direct_supported(const PwArgs& a);
-int launch_pw_direct(const PwArgs& a, hipStream_t s);
-bool pw_se_fold_supported(int cin, int cout, int squeeze, int hw);
+bool pw_se_fold_supported(int cin, int cout, int squeeze, int hw);      // the projection's launch would compute the squeeze-excitation in its prologue
 int launch_pointwise_group(const PwArgs* arr, int count, bool conv, hipStream_t s);
-// 256x256-tile implicit GEMM for the MFMA-bound dense convs (convbig.hip)
-bool conv_big_supported(const PwArgs& a);
-int launch_conv_big(const PwArgs& a, hipStream_t s);
-// 3x3 "same" conv followed by MaxPool2d(2, 2) in one launch (the 16 x 16 output block of the patch kernel pools to 8 x 8 in its
-// epilogue): true where launch_conv_big would take the patch kernel for this geometry at every batch size
-bool conv_patch_pool_ok(int cin, int cout, int h, int w);
-bool conv_pool_ok(int cin, int cout, int h, int w);             // conv 3x3 + MaxPool2d(2, 2) in one launch: the patch kernel or the run-staged 256 x 256 tile
-bool conv_halo_pool_ok(int cin, int cout, int h, int w);        // ... the run-staged tile's form: may also write the conv output itself (a.out set)
+// 3x3 "same" conv followed by MaxPool2d(2, 2) in one launch
+bool conv_patch_pool_ok(int cin, int cout, int h, int w);       // on the patch kernel, which then does NOT write the conv output itself
+bool conv_halo_pool_ok(int cin, int cout, int h, int w);        // on the run-staged 256 x 256 tile: may also write the conv output itself (a.out set)
+bool conv_pool_ok(int cin, int cout, int h, int w);             // either
 int launch_conv_pool(const PwArgs& a, hipStream_t s);          // a.pool_out set
+// dense fp32 head (with or without a rider in w_b) on the run-staged tiles
 bool conv_head_big_supported(const PwArgs& a);
 int launch_conv_head_big(const PwArgs& a, hipStream_t s);
 struct DwArgs;
@@ -310,7 +306,6 @@ int launch_l2norm(const half_t* x, const float* scale, half_t* out, long pixels,
 int launch_u8hwc_to_planar(const unsigned char* in, float* out, float* scale_xy, int n, int h, int w, int oh, int ow, hipStream_t s);
 int launch_resize_bilinear(const float* in, float* out, float* scale_xy, int n, int h, int w, int oh, int ow, hipStream_t s);
 
-// fused inverted-residual block (fused.hip): [expand 1x1] -> depthwise -> [project 1x1 (+residual)]
 // run of tiny layers (<= 32 output pixels each) executed by one workgroup per image with the activations in LDS (tail.hip)
 constexpr int TAIL_MAX_OPS = 16;
 struct TailOp {

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "choice.h"
 
 #ifdef DN_DEV_STAMPS
 static long long* g_patch_stamps = nullptr;     // dev build only (tools/probe_patch.py): per-workgroup phase stamps [workgroup][8]
@@ -194,6 +195,7 @@ __device__ __forceinline__ void conv_epilogue_fp32(floatx16 (&acc)[TC][TP], cons
 typedef __attribute__((address_space(1))) const void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 constexpr int GK = 64;                      // K per stage
+static_assert(BP == CONV_BIG_TILE && BC == CONV_BIG_TILE && GK == CONV_GLDS_K, "choice.h states the tile of conv_glds_kernel");
 constexpr int GSTAGE = (BP + BC) * GK;      // halfs per stage buffer (64 KB)
 
 // HEAD: the 1x1 class head of a large pyramid level with fp32 [anchor][class] output (SSDLite, generalized_ssd.py:60-74): any
@@ -399,9 +401,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // The weights are then most of the traffic, and their bytes per flop fall with the PIXEL tile only: a wave tile of TP pixel tiles x
 // TC channel tiles (workgroup 64 TP pixels x 64 TC channels) is instantiated as 4 x 4 (256 x 256) and 8 x 2 (512 x 128).
 constexpr int HK = 32;                      // K per half-stage
-// capacity of a staged run in rows (2 runs + 2 x 2 weight half-stages + 1 KB <= 152 KB of LDS). Unused DMA slots still cost an issue
-// each: 512 x 128 keeps the 832 rows its layers need (W <= 159; with 960 it spills and loses 8 %)
-constexpr int halo_run_rows(int tp, int tc) { return tc == 4 ? 704 : tp == 8 ? 832 : 960; }
+// (capacity of a staged run in rows: halo_run_rows, choice.h -- the tile choice needs it too)
 
 template <int KSZ, int TP, int TC, bool HEAD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv_halo_kernel(PwArgs a) {
@@ -1130,11 +1130,6 @@ __global__ __launch_bounds__(256) void conv_patch_resident_kernel(PwArgs a, int 
     CP_STAMP(2);
 }
 
-bool patch_resident_shape(const PwArgs& a) {
-    const long out_bytes = (long)(a.m / a.hw) * (a.pool_out ? (a.cv_h >> 1) * (a.cv_w >> 1) : a.cv_h * a.cv_w) * a.cout * 2;
-    return a.cv_cin == 64 && a.act == DN_ACT_RELU && out_bytes < 0xFFFFFFF0L && (long)a.cv_h * a.cv_w * 128 < (1L << 31) && dn_knob("DN_PATCH_RESIDENT", 1) != 0;
-}
-
 int launch_patch_resident(const PwArgs& a, hipStream_t s) {
     const int tiles_x = dn_cdiv(a.cv_w, PT), tiles = tiles_x * dn_cdiv(a.cv_h, PT);
     const long ntiles = (long)tiles * (a.m / a.hw);
@@ -1155,16 +1150,7 @@ int launch_patch_resident(const PwArgs& a, hipStream_t s) {
     return DN_OK;
 }
 
-int patch_max_cin() { return 128; }
-
-bool patch_shape(const PwArgs& a) {
-    const int on = 1;
-    return on && a.zeros && !a.out_fp32 && !a.residual && !a.se && a.cv_k == 3 && a.cv_stride == 1 && a.cv_pad == 1 && a.cv_dil == 1 &&
-           a.cv_ho == a.cv_h && a.cv_wo == a.cv_w && a.cv_cin % 64 == 0 && a.cv_cin <= patch_max_cin() && a.cout % 64 == 0 && a.m / a.hw <= 65535;
-}
-
 int launch_patch(const PwArgs& a, hipStream_t s) {
-    if (patch_resident_shape(a)) return launch_patch_resident(a, s);
     const size_t lds = PATCH_LDS;
     DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(conv_patch_kernel)));
     dn_note_kernel("conv_patch_kernel");
@@ -1172,15 +1158,6 @@ int launch_patch(const PwArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(conv_patch_kernel, dim3(tiles, a.cout / 64, a.m / a.hw), dim3(256), lds, s, a, patch_stamps_take((size_t)tiles * (a.cout / 64) * (a.m / a.hw)));
     return DN_OK;
 }
-}  // namespace
-
-namespace {
-bool halo_shape(const PwArgs& a) {
-    const int halo = dn_knob("DN_CONV_HALO", 1);
-    return halo && a.zeros && a.cv_k == 3 && a.cv_stride == 1 && a.cv_pad == a.cv_dil && a.cv_ho == a.cv_h && a.cv_wo == a.cv_w &&
-           a.cv_cin % 64 == 0 && (long)a.m * a.cv_cin * 2 < (1L << 31) && (long)(a.cout + a.cout_b) * a.cin * 2 < (1L << 32);
-}
-int halo_rows(const PwArgs& a) { return 2 * (a.cv_pad * a.cv_w + a.cv_pad); }
 
 template <int TP, int TC, bool HEAD>
 int launch_halo(const PwArgs& a, hipStream_t s, const char* name) {
@@ -1195,86 +1172,61 @@ int launch_halo(const PwArgs& a, hipStream_t s, const char* name) {
     hipLaunchKernelGGL((conv_halo_kernel<3, TP, TC, HEAD>), dim3(dn_cdiv(a.m, BPt), dn_cdiv(a.cout + (HEAD ? a.cout_b : 0), BCt)), dim3(256), lds, s, b);
     return DN_OK;
 }
-
-// which tile a fp16-output 3x3 stride-1 conv runs on: 0 none, 1 = 256 x 256, 2 = 512 x 128, 3 = 256 x 128
-int halo_variant(const PwArgs& a) {
-    if (a.out_fp32 || a.residual || a.se || !halo_shape(a)) return 0;
-    const int hr = halo_rows(a);
-    const int force = 0;      // dev knob: prefer the 512 x 128 (2) / 256 x 128 (3) tile where it applies
-    if (force == 2 && a.cout % 128 == 0 && a.cv_cin >= 128 && 512 + hr <= halo_run_rows(8, 2)) return 2;
-    if (force == 3 && a.cout % 128 == 0 && a.cv_cin >= 128 && 256 + hr <= halo_run_rows(4, 2)) return 3;
-    if (a.cout % 256 == 0 && 256 + hr <= halo_run_rows(4, 4)) return 1;
-    if (a.cout % 128 == 0 && a.cv_cin >= 128 && 512 + hr <= halo_run_rows(8, 2)) return 2;
-    if (a.cout % 128 == 0 && a.cv_cin >= 128 && 256 + hr <= halo_run_rows(4, 2)) return 3;      // (one 64-channel iteration: measured level with the 128x128 tile)
-    // (a 256 x 64 tile for the 64-channel layer conv1_2: 330 vs 388 TFLOP/s for the 128 x 64 tile of pointwise.hip -- four MFMAs per K
-    // step cannot cover the fragment masks and reads)
-    return 0;
-}
 }  // namespace
 
-bool conv_big_supported(const PwArgs& a) {
-    if (halo_variant(a) || patch_shape(a)) return true;
-    return a.zeros && a.cv_cin % GK == 0 && a.cout % BC == 0 && !a.out_fp32 && !a.residual && !a.se && a.cv_k * a.cv_k <= 32 && a.cin >= 2 * GK &&
-           (long)a.m / a.hw * a.cv_h * a.cv_w * a.cv_cin * 2 < (1L << 31) && (long)a.cout * a.cin * 2 < (1L << 32);
-}
-
-int launch_conv_big(const PwArgs& a, hipStream_t s) {
-    // 64 input channels: always the patch kernel; 128: where the run kernel would need its 256 x 128 tile (maps wider than 159; measured:
-    // conv2_2 of ssd512 882 vs 568 TFLOP/s, while the 512 x 128 run tile of the 150-wide map keeps the faster step)
-    if (patch_shape(a) && (a.cv_cin <= 64 || halo_variant(a) == 0 || halo_variant(a) == 3)) return launch_patch(a, s);
-    switch (halo_variant(a)) {
-        case 1: return launch_halo<4, 4, false>(a, s, "conv_halo_kernel<3,4,4>");
-        case 2: return launch_halo<8, 2, false>(a, s, "conv_halo_kernel<3,8,2>");
-        case 3: return launch_halo<4, 2, false>(a, s, "conv_halo_kernel<3,4,2>");
+// the convbig.hip arms of the dense-conv launchers' switch (choice.h: conv_choose)
+int launch_conv_big(const PwArgs& a, const PwChoice& c, hipStream_t s) {
+    switch (c.kernel) {
+        case PwChoice::CONV_PATCH: return launch_patch(a, s);
+        case PwChoice::CONV_PATCH_RESIDENT: return launch_patch_resident(a, s);
+        case PwChoice::CONV_HALO:
+            switch (c.halo * 2 + (c.head ? 1 : 0)) {
+                case 2: return launch_halo<4, 4, false>(a, s, "conv_halo_kernel<3,4,4>");
+                case 4: return launch_halo<8, 2, false>(a, s, "conv_halo_kernel<3,8,2>");
+                case 6: return launch_halo<4, 2, false>(a, s, "conv_halo_kernel<3,4,2>");
+                case 3: return launch_halo<4, 4, true>(a, s, "conv_halo_kernel<3,4,4,head>");
+                case 5: return launch_halo<8, 2, true>(a, s, "conv_halo_kernel<3,8,2,head>");
+                case 7: return launch_halo<4, 2, true>(a, s, "conv_halo_kernel<3,4,2,head>");
+                default: break;
+            }
+            break;
+        case PwChoice::CONV_GLDS: {
+            DN_REQUIRE(a.cout % BC == 0, "conv: cout=%d not a multiple of 256 on the 256x256 tile", a.cout);
+            const size_t otile = (size_t)BP * OROW, st = (size_t)2 * GSTAGE;
+            const size_t lds = (st > otile ? st : otile) * sizeof(half_t) + BC * sizeof(float);
+            DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(conv_glds_kernel<false>)));
+            dn_note_kernel("conv_glds_kernel");
+            hipLaunchKernelGGL(conv_glds_kernel<false>, dim3(dn_cdiv(a.m, BP), a.cout / BC), dim3(256), lds, s, a);
+            return DN_OK;
+        }
         default: break;
     }
-    DN_REQUIRE(a.cout % BC == 0, "conv: cout=%d not a multiple of 256 on the 256x256 tile", a.cout);
-    const size_t otile = (size_t)BP * OROW, st = (size_t)2 * GSTAGE;
-    const size_t lds = (st > otile ? st : otile) * sizeof(half_t) + BC * sizeof(float);
-    DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(conv_glds_kernel<false>)));
-    dn_note_kernel("conv_glds_kernel");
-    hipLaunchKernelGGL(conv_glds_kernel<false>, dim3(dn_cdiv(a.m, BP), a.cout / BC), dim3(256), lds, s, a);
-    return DN_OK;
+    dn_set_error("conv: no 256 x 256-tile kernel for cin=%d cout=%d on %d x %d", a.cv_cin, a.cout, a.cv_h, a.cv_w);
+    return DN_E_UNSUPPORTED;
 }
 
-// Dense 3x3 heads with fp32 outputs (SSDHead, generalized_ssd.py:77-92) on the run-staged 256x256 tile; channel tiles beyond cout
-// compute on the last weight row and are not stored.
+// ---- plan time: what the launches below WILL take, asked of conv_choose about a one-image 3 x 3 "same" conv
+// conv + MaxPool2d(2, 2) in one launch on the patch kernel (its 16 x 16 output block pools to 8 x 8 in the epilogue): where the plain conv takes the patch
+// kernel -- at every batch size: a larger batch can only take the run-staged tiles away (their 2 GB addressing limit), never the patch kernel
 bool conv_patch_pool_ok(int cin, int cout, int h, int w) {
-    if (!dn_knob("DN_CONV_BIG", 1) || !dn_knob("DN_CONV_POOL", 1) || (h & 1) || (w & 1)) return false;
-    static const half_t dummy_zero[8] = {};
-    PwArgs a{};
-    a.cv_k = 3; a.cv_stride = 1; a.cv_pad = 1; a.cv_dil = 1; a.cv_h = a.cv_ho = h; a.cv_w = a.cv_wo = w; a.cv_cin = cin;
-    a.zeros = dummy_zero; a.residual = nullptr; a.se = nullptr; a.out_fp32 = 0;
-    a.hw = h * w; a.m = a.hw; a.cin = 9 * cin; a.cout = cout;
-    // the patch kernel is what launch_conv_big picks when the run-staged 512 x 128 tile does not apply; a larger batch can only
-    // take the run-staged tiles away (their 2 GB addressing limit), never the patch kernel
-    return patch_shape(a) && (cin <= 64 || halo_variant(a) == 0 || halo_variant(a) == 3) && (long)dn_cdiv(a.m, 256) * dn_cdiv(cout, 256) >= 40;
+    if (!dn_knob("DN_CONV_POOL", 1) || (h & 1) || (w & 1)) return false;
+    const PwChoice::Kernel k = conv_choose(conv3x3_query(cin, cout, h, w), CONV_PLAIN).kernel;
+    return k == PwChoice::CONV_PATCH || k == PwChoice::CONV_PATCH_RESIDENT;
 }
-
-// ... or, for the layers of the run-staged 256 x 256 tile (conv3_3 of ssd512: 256 channels on 128 x 128), in the epilogue of conv_halo_kernel<3,4,4>:
-// the tile must be whole row pairs of one image (256 % 2W == 0, H W % 256 == 0)
-static bool conv_halo_pool_geometry(int cin, int cout, int h, int w) {
-    if ((h & 1) || (w & 1)) return false;
-    static const half_t dummy_zero[8] = {};
-    PwArgs a{};
-    a.cv_k = 3; a.cv_stride = 1; a.cv_pad = 1; a.cv_dil = 1; a.cv_h = a.cv_ho = h; a.cv_w = a.cv_wo = w; a.cv_cin = cin;
-    a.zeros = dummy_zero; a.residual = nullptr; a.se = nullptr; a.out_fp32 = 0;
-    a.hw = h * w; a.m = a.hw; a.cin = 9 * cin; a.cout = cout;
-    return halo_variant(a) == 1 && !(patch_shape(a) && cin <= 64) && 256 % (2 * w) == 0 && (h * w) % 256 == 0 &&
-           (long)dn_cdiv(a.m, 256) * dn_cdiv(cout, 256) >= 40;
-}
-// (the knobs decide at plan creation; the launch only checks the geometry, so a knob flipped between dn_create and dn_forward cannot strand a fused pair)
+// ... or in the epilogue of conv_halo_kernel<3,4,4>: where the pooled launch takes the run-staged tile. The knobs decide HERE, at plan creation
+// (conv_choose, CONV_POOLED)
 bool conv_halo_pool_ok(int cin, int cout, int h, int w) {
-    return dn_knob("DN_CONV_BIG", 1) && dn_knob("DN_CONV_POOL", 1) && dn_knob("DN_CONV_HALO_POOL", 1) && conv_halo_pool_geometry(cin, cout, h, w);
+    return dn_knob("DN_CONV_BIG", 1) && dn_knob("DN_CONV_POOL", 1) && dn_knob("DN_CONV_HALO_POOL", 1) &&
+           conv_choose(conv3x3_query(cin, cout, h, w), CONV_POOLED).kernel == PwChoice::CONV_HALO;
 }
 bool conv_pool_ok(int cin, int cout, int h, int w) { return conv_patch_pool_ok(cin, cout, h, w) || conv_halo_pool_ok(cin, cout, h, w); }
 
 int launch_conv_pool(const PwArgs& a, hipStream_t s) {
     DN_REQUIRE(a.pool_out && !(a.cv_h & 1) && !(a.cv_w & 1), "conv + max-pool: needs the pooled output and an even map");
-    // by geometry alone: the patch kernel never writes the full-resolution map (a pair whose map has other readers is only fused when the run-staged
-    // tile takes it: plan.hip), so a.out -- non-null for EVERY tensor with DN_WS_REUSE=0 -- must not steer the choice
-    if (patch_shape(a) && (a.cv_cin <= 64 || !conv_halo_pool_geometry(a.cv_cin, a.cout, a.cv_h, a.cv_w))) return launch_patch(a, s);
-    DN_REQUIRE(conv_halo_pool_geometry(a.cv_cin, a.cout, a.cv_h, a.cv_w), "conv + max-pool: geometry not supported by the patch kernel or the run-staged tile");
+    const PwChoice c = conv_choose(a, CONV_POOLED);
+    DN_REQUIRE(c.kernel != PwChoice::NONE, "conv + max-pool: geometry not supported by the patch kernel or the run-staged tile");
+    if (const int rc = pw_check_honoured(a, c, "conv + max-pool")) return rc;
+    if (c.kernel != PwChoice::CONV_HALO) return launch_conv_big(a, c, s);
     // the run-staged tile addresses its input with 31-bit byte offsets: a batch beyond that goes in image ranges
     const int n = a.m / a.hw;
     const long per_img = (long)a.hw * a.cv_cin * 2;
@@ -1286,44 +1238,21 @@ int launch_conv_pool(const PwArgs& a, hipStream_t s) {
         b.x = a.x + (size_t)i0 * a.hw * a.cv_cin;
         b.pool_out = a.pool_out + (size_t)i0 * (a.hw / 4) * a.cout;
         if (a.out) b.out = reinterpret_cast<half_t*>(a.out) + (size_t)i0 * a.hw * a.cout;
-        DN_REQUIRE(halo_variant(b) == 1, "conv + max-pool: the run-staged 256 x 256 tile does not take %d x %d x %d", a.cv_h, a.cv_w, a.cv_cin);
-        const int rc = launch_halo<4, 4, false>(b, s, "conv_halo_kernel<3,4,4>");
+        DN_REQUIRE(halo_variant(b) == c.halo, "conv + max-pool: the run-staged 256 x 256 tile does not take %d x %d x %d", a.cv_h, a.cv_w, a.cv_cin);
+        const int rc = launch_conv_big(b, c, s);
         if (rc != DN_OK) return rc;
     }
     return DN_OK;
 }
 
-// Tile of a dense fp32 head launch: 0 none, 1 = 256 px x 256 ch, 2 = 512 x 128, 3 = 256 x 128. The class + box channels of a level (380 / 570
-// for 91 classes) fill 74 % of two / three 256-channel tiles but 99 % / 89 % of three / five 128-channel tiles, and the 512 x 128 run tile
-// runs level with the 256 x 256 one per FLOP (conv3 .. conv5 of ssd512_vgg16: 1140-1330 vs 1150-1320 TFLOP/s): the idle channels were a
-// quarter of the head launches' time. A level too small for half the chip in 512-pixel tiles (the 16 x 16 level of ssd512 at batch 32: 80
-// workgroups) takes 256 x 128 tiles -- twice the workgroups at half the work each.
-static int head_variant(const PwArgs& a) {
-    const int on = dn_knob("DN_CONV_HEAD_BIG", 1);
-    const int minwg = 40;
-    if (!on || !a.out_fp32 || a.residual || a.se || !halo_shape(a) || (a.cout & 1)) return 0;
-    const int hr = halo_rows(a), nc = a.cout + a.cout_b;
-    const int c256 = dn_cdiv(nc, 256), c128 = dn_cdiv(nc, 128);
-    const long p256 = dn_cdiv(a.m, 256), p512 = dn_cdiv(a.m, 512);
-    const int narrow = dn_knob("DN_CONV_HEAD_NARROW", 1);
-    if (narrow && c128 * 128 < c256 * 256 && a.cv_cin >= 128) {
-        if (512 + hr <= halo_run_rows(8, 2) && p512 * c128 >= 128) return 2;
-        if (256 + hr <= halo_run_rows(4, 2) && p256 * c128 >= 2 * minwg) return 3;      // (40 workgroups of the 8 x 8 level: slower than the group launch)
-    }
-    const int tiles = dn_cdiv(a.cout, 256);
-    if (256 + hr <= halo_run_rows(4, 4) && a.cout * 10 >= tiles * 256 * 6 && p256 * tiles >= minwg) return 1;      // at most 40 % of the channel tiles idle
-    return 0;
-}
-
-bool conv_head_big_supported(const PwArgs& a) { return head_variant(a) != 0; }
+bool conv_head_big_supported(const PwArgs& a) { return conv_choose(a, CONV_HEAD).kernel != PwChoice::NONE; }
 
 int launch_conv_head_big(const PwArgs& a, hipStream_t s) {
-    switch (head_variant(a)) {
-        case 1: return launch_halo<4, 4, true>(a, s, "conv_halo_kernel<3,4,4,head>");
-        case 2: return launch_halo<8, 2, true>(a, s, "conv_halo_kernel<3,8,2,head>");
-        case 3: return launch_halo<4, 2, true>(a, s, "conv_halo_kernel<3,4,2,head>");
-        default: break;
+    const PwChoice c = conv_choose(a, CONV_HEAD);
+    if (c.kernel == PwChoice::NONE) {
+        dn_set_error("dense head: not supported by the run-staged tiles");
+        return DN_E_UNSUPPORTED;
     }
-    dn_set_error("dense head: not supported by the run-staged tiles");
-    return DN_E_UNSUPPORTED;
+    if (const int rc = pw_check_honoured(a, c, "dense head")) return rc;
+    return launch_conv_big(a, c, s);
 }

@@ -816,9 +816,6 @@ int launch_ks(const ExpDwArgs& a, int oh, int ow, hipStream_t s) {
 }  // namespace
 
 void expdw_tile(int Ho, int Wo, int stride, int* oh, int* ow, int proj_cout = 0) {
-    // dev knob: DN_EXPDW_TILE = 48 / 88 forces the 4 x 8 / 8 x 8 output tile on the large maps (tile-size experiments)
-    const int force = 0;
-    if (force && Wo >= 32 && Ho >= 32) { *oh = force / 10; *ow = force % 10; return; }
     if (Wo <= 5 && Ho <= 5) { *oh = 5; *ow = 5; }
     else if (Wo <= 10) { *oh = 5; *ow = 10; }
     else if (Wo < 32 && Wo % 16 != 0) {                     // 19x19 / 20x20 maps: 10-wide tiles waste nothing

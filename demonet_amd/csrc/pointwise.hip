@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "choice.h"
 
 // dev hooks: exported and compiled into the kernels only by the dev build (python -m demonet_amd.build --stamps, -DDN_DEV_STAMPS)
 #ifdef DN_DEV_STAMPS
@@ -855,128 +856,26 @@ int launch_xs(const PwArgs& a, hipStream_t s) {
     return DN_OK;
 }
 
-template <int BP, int BC, int WP, int WC, bool CONV, int BK, int PF = 1, bool SEF = false>
-int launch_bk(const PwArgs& a, hipStream_t s, int nbuf) {
+// pw_kernel<BP, BC, WP, WC, CONV, BK, PF, SEF, FK>: double-buffered K staging in LDS; FK adds the SE scales of the tile's two images
+template <int BP, int BC, int WP, int WC, bool CONV, int BK, int PF, bool SEF, bool FK>
+int launch_tile(const PwArgs& a0, hipStream_t s) {
+    PwArgs a = a0;
+    a.stamps = g_pw_stamps;         // dev hook (null unless a probe set it)
     const int tiles = pw_row_tiles(a, BP);
     dim3 grid((a.xq > 0 ? 8 * tiles : tiles) * dn_cdiv(a.cout, BC));
-    size_t halfs = (size_t)nbuf * (BP + BC) * (BK + 8);
+    size_t halfs = (size_t)2 * (BP + BC) * (BK + 8);
     const size_t otile = (a.out_fp32 || a.residual) ? (size_t)2 * BP * (BC + 4) : (size_t)BP * (BC + 8);     // epilogue staging tile, in halfs (fp32 for head rows and for residual layers)
     if (otile > halfs) halfs = otile;
-    const size_t lds = halfs * sizeof(half_t) + BC * sizeof(float) + (SEF ? 832 * sizeof(float) : 0);
-    if (lds > 64 * 1024) DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(pw_kernel<BP, BC, WP, WC, CONV, BK, PF, SEF>)));
+    const size_t lds = halfs * sizeof(half_t) + BC * sizeof(float) + (SEF ? 832 * sizeof(float) : 0) + (FK && a.se ? (size_t)2 * a.cin * sizeof(float) : 0);
+    if (lds > 64 * 1024) DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(pw_kernel<BP, BC, WP, WC, CONV, BK, PF, SEF, FK>)));
     dn_note_kernel(SEF ? "pw_kernel<%d,%d,%d,%d,%s,%d,%d,true>" : PF > 1 ? "pw_kernel<%d,%d,%d,%d,%s,%d,%d>" : "pw_kernel<%d,%d,%d,%d,%s,%d>", BP, BC, WP, WC,
                    CONV ? "true" : "false", BK, PF);
-    if constexpr (!CONV && !SEF && (PF == 3 || PF == 4)) {
-        // the bound-test-free K loop (pw_body FK): whole 32-deep stages, no SE-scaled staging, 32-bit byte offsets
-        if (dn_knob("DN_PW_FASTK", 1) && a.cin % BK == 0 && (!a.se || a.hw >= BP) && !(a.act >> 8) && (size_t)a.m * a.cin < (1u << 30) && (size_t)a.cout * a.cin < (1u << 30)) {
-            const size_t lds_fk = lds + (a.se ? (size_t)2 * a.cin * sizeof(float) : 0);      // + the SE scales of the tile's two images
-            if (lds_fk > 64 * 1024) DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(pw_kernel<BP, BC, WP, WC, CONV, BK, PF, SEF, true>)));
-            hipLaunchKernelGGL((pw_kernel<BP, BC, WP, WC, CONV, BK, PF, SEF, true>), grid, dim3(256), lds_fk, s, a, tiles);
-            return DN_OK;
-        }
-    }
-    hipLaunchKernelGGL((pw_kernel<BP, BC, WP, WC, CONV, BK, PF, SEF>), grid, dim3(256), lds, s, a, tiles);
+    hipLaunchKernelGGL((pw_kernel<BP, BC, WP, WC, CONV, BK, PF, SEF, FK>), grid, dim3(256), lds, s, a, tiles);
     return DN_OK;
 }
 
-// 32-deep double-buffered K staging. (Measured and dropped: a single exact-K stage for K <= 128 -- no load/compute overlap,
-// slower; 64-deep double buffer -- lost to occupancy.)
-template <int BP, int BC, int WP, int WC, bool CONV>
-int launch_cfg(const PwArgs& a, hipStream_t s) {
-    const_cast<PwArgs&>(a).stamps = g_pw_stamps;
-    if constexpr (CONV && BP == 128 && BC == 128) {
-        // MFMA-bound dense convolutions (VGG): 64-deep stages halve the barriers per MFMA; the tile is register-limited to two
-        // workgroups per CU either way, and 2 x 74 KB of LDS fit
-        const int bk64 = 1;
-        if (bk64 && a.cv_cin % 64 == 0) return launch_bk<BP, BC, WP, WC, CONV, 64>(a, s, 2);
-    }
-    return launch_bk<BP, BC, WP, WC, CONV, 32>(a, s, 2);
-}
-
-
-}  // namespace
-
-// Tile choice: these GEMMs are latency/HBM-bound, not MFMA-bound, so what matters is (a) enough workgroups to fill
-// 256 CUs several times over and (b) not re-reading x for many channel tiles. Prefer the largest tile that still
-// gives >= ~1500 workgroups, else fall back to smaller tiles.
-template <bool CONV>
-int launch_select(const PwArgs& a, hipStream_t s) {
-    auto wgs = [&](int bp, int bc) { return (long)dn_cdiv(a.m, bp) * dn_cdiv(a.cout, bc); };
-    switch (g_pw_tile) {
-        case 1: return launch_cfg<256, 32, 4, 1, CONV>(a, s);
-        case 2: return launch_cfg<128, 32, 4, 1, CONV>(a, s);
-        case 3: return launch_cfg<128, 64, 4, 1, CONV>(a, s);
-        case 4: return launch_cfg<64, 64, 2, 2, CONV>(a, s);
-        case 5: return launch_cfg<128, 128, 2, 2, CONV>(a, s);
-        case 6: return launch_cfg<64, 128, 2, 2, CONV>(a, s);
-        case 7: if constexpr (!CONV) return launch_cfg<128, 96, 4, 1, CONV>(a, s); break;
-        default: break;
-    }
-    if constexpr (!CONV) {
-        // 1x1 convs with a thin side (cin < 256 or cout < 128) are HBM/latency-bound: tools/tune_pw.py over every layer shape
-        // of the model shows the small tiles (most workgroups, fewest registers: 64 VGPRs -> 8 waves/SIMD) winning or tying
-        // everywhere, 128x32 when there is a single channel tile. The big tiles only pay off for MFMA-bound shapes.
-        if (a.cin < 256 || a.cout < 128) {
-            const int shortk = 1;
-            if (shortk && a.cin > 32 && a.cin <= 128) {       // 2..4 K stages: all loads up front
-                const_cast<PwArgs&>(a).stamps = g_pw_stamps;
-                if constexpr (!CONV) {
-                    if (a.sef_part) return launch_bk<64, 64, 2, 2, CONV, 32, 4, true>(a, s, 2);     // squeeze-excitation folded in (pw_se_fold_supported)
-                }
-                if (a.cout <= 32) return launch_bk<128, 32, 4, 1, CONV, 32, 4>(a, s, 2);
-                return launch_bk<64, 64, 2, 2, CONV, 32, 4>(a, s, 2);
-            }
-            if (shortk && a.cin > 128) {                      // long K on a thin layer: loads 4 stages ahead
-                const_cast<PwArgs&>(a).stamps = g_pw_stamps;
-                if (a.cout <= 32) return launch_bk<128, 32, 4, 1, CONV, 32, 4>(a, s, 2);
-                return launch_bk<64, 64, 2, 2, CONV, 32, 4>(a, s, 2);
-            }
-            if (a.cout <= 32) return launch_cfg<128, 32, 4, 1, CONV>(a, s);
-            return launch_cfg<64, 64, 2, 2, CONV>(a, s);
-        }
-    }
-    if constexpr (CONV) {
-        const int big = dn_knob("DN_CONV_BIG", 1);
-        const int bigmin = 40;       // measured on both VGG models: 40 < 90 < 200; the sub-batch chains fill the chip together
-        if (big && conv_big_supported(a) && wgs(256, 256) >= bigmin) return launch_conv_big(a, s);
-    }
-    if (a.cout <= 32) {
-        if (wgs(256, 32) >= 1500) return launch_cfg<256, 32, 4, 1, CONV>(a, s);
-        return launch_cfg<128, 32, 4, 1, CONV>(a, s);
-    }
-    if (a.cout <= 64) {
-        if (wgs(128, 64) >= 1500) return launch_cfg<128, 64, 4, 1, CONV>(a, s);
-        return launch_cfg<64, 64, 2, 2, CONV>(a, s);
-    }
-    if constexpr (CONV) {
-        // small dense convs (the extras of the VGG models: <= 16 x 16 maps, K = 9 cin up to 4608): a few workgroups walking 70 - 140
-        // K stages, each an exposed memory round trip with the plain double buffer (60 - 130 us per layer for < 1 us of MFMA work):
-        // request the stages 4 ahead through the register ring of the short-K pointwise variant
-        if (a.cout > 32 && wgs(64, 64) < 512) return launch_bk<64, 64, 2, 2, CONV, 32, 4>(a, s, 2);
-    }
-    if constexpr (!CONV) {
-        // a 1x1 layer with few workgroups and a long K (the first extras layer: 480 -> 256 on 10 x 10) is a chain of exposed round trips with the plain
-        // double buffer: stages requested 4 ahead on the bound-test-free loop. Measured (round 3): the launch 18.8 -> 14 us, one forward at a time -5 us,
-        // with three forwards in flight 0.2 - 0.3 % slower in three of three pairs: opt-in
-        if (dn_knob("DN_PW_LONGK_PF", 0) && a.cin % 32 == 0 && a.cin >= 256 && a.cout > 32 && wgs(64, 64) < 1500) {
-            const_cast<PwArgs&>(a).stamps = g_pw_stamps;
-            return launch_bk<64, 64, 2, 2, CONV, 32, 4>(a, s, 2);
-        }
-    }
-    const int t128 = 300;      // min workgroups for the 128x128 tile of the MFMA-bound dense convs (measured on the VGG models)
-    if (wgs(128, 128) >= (CONV ? t128 : 1500)) return launch_cfg<128, 128, 2, 2, CONV>(a, s);
-    if (wgs(128, 64) >= 1500 || a.cout % 128 > 64 || a.cout % 128 == 0) {
-        if (wgs(64, 128) >= 600) return launch_cfg<64, 128, 2, 2, CONV>(a, s);
-    }
-    return launch_cfg<64, 64, 2, 2, CONV>(a, s);
-}
-
-namespace {
-template <int BP, int BC, int WP, int WC, bool CONV, int BK = 32, int GPF_ = 0>
-int launch_group_cfg(const PwArgs* arr, int count, hipStream_t s) {
-    // head 1x1 convs have long K (21 stages at level 0): loads run 3 stages ahead (the dense-conv heads of the VGG models are
-    // MFMA-bound at 184 VGPRs and keep the plain double buffer -- except the small levels, below)
-    constexpr int GPF = GPF_ ? GPF_ : (CONV ? 1 : 3);
+template <int BP, int BC, int WP, int WC, bool CONV, int BK, int GPF, bool FK>
+int launch_group_tile(const PwArgs* arr, int count, hipStream_t s) {
     PwGroup g{};
     g.count = count;
     int acc = 0;
@@ -999,65 +898,77 @@ int launch_group_cfg(const PwArgs* arr, int count, hipStream_t s) {
     if (otile > halfs) halfs = otile;
     const size_t lds = halfs * sizeof(half_t) + BC * sizeof(float);
     dn_note_kernel(GPF > 1 ? "pw_group_kernel<%d,%d,%d,%d,%s,%d,%d>" : "pw_group_kernel<%d,%d,%d,%d,%s,%d>", BP, BC, WP, WC, CONV ? "true" : "false", BK, GPF);
-    if constexpr (!CONV && GPF == 3) {
-        // every problem on the bound-test-free K loop (whole 32-deep stages, no SE-scaled staging, 32-bit byte offsets): the instantiation that holds nothing else
-        bool fk = dn_knob("DN_PW_FASTK", 1) != 0;
-        for (int i = 0; i < count; ++i)
-            fk &= arr[i].cin % BK == 0 && !arr[i].se && !(arr[i].act >> 8) && (size_t)arr[i].m * arr[i].cin < (1u << 30) && (size_t)arr[i].cout * arr[i].cin < (1u << 30);
-        if (fk) {
-            if (lds > 64 * 1024) DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(pw_group_kernel<BP, BC, WP, WC, CONV, BK, GPF, true>)));
-            hipLaunchKernelGGL((pw_group_kernel<BP, BC, WP, WC, CONV, BK, GPF, true>), dim3(acc), dim3(256), lds, s, g);
-            return DN_OK;
-        }
-    }
-    if (lds > 64 * 1024) DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(pw_group_kernel<BP, BC, WP, WC, CONV, BK, GPF>)));
-    hipLaunchKernelGGL((pw_group_kernel<BP, BC, WP, WC, CONV, BK, GPF>), dim3(acc), dim3(256), lds, s, g);
+    if (lds > 64 * 1024) DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(pw_group_kernel<BP, BC, WP, WC, CONV, BK, GPF, FK>)));
+    hipLaunchKernelGGL((pw_group_kernel<BP, BC, WP, WC, CONV, BK, GPF, FK>), dim3(acc), dim3(256), lds, s, g);
     return DN_OK;
 }
+
+// Every instantiation a choice can name, one line each: BP, BC, WP, WC, CONV, BK, PF, SEF, FK
+#define PW_TILES(X)                                                                                                                              \
+    X(256, 32, 4, 1, false, 32, 1, false, false) X(128, 32, 4, 1, false, 32, 1, false, false) X(128, 64, 4, 1, false, 32, 1, false, false)        \
+    X(64, 64, 2, 2, false, 32, 1, false, false) X(128, 128, 2, 2, false, 32, 1, false, false) X(64, 128, 2, 2, false, 32, 1, false, false)        \
+    X(128, 96, 4, 1, false, 32, 1, false, false)                                                                                                  \
+    X(128, 32, 4, 1, false, 32, 4, false, false) X(128, 32, 4, 1, false, 32, 4, false, true)                                                      \
+    X(64, 64, 2, 2, false, 32, 4, false, false) X(64, 64, 2, 2, false, 32, 4, false, true) X(64, 64, 2, 2, false, 32, 4, true, false)             \
+    X(256, 32, 4, 1, true, 32, 1, false, false) X(128, 32, 4, 1, true, 32, 1, false, false) X(128, 64, 4, 1, true, 32, 1, false, false)           \
+    X(64, 64, 2, 2, true, 32, 1, false, false) X(128, 128, 2, 2, true, 32, 1, false, false) X(64, 128, 2, 2, true, 32, 1, false, false)           \
+    X(128, 128, 2, 2, true, 64, 1, false, false) X(64, 64, 2, 2, true, 32, 4, false, false)
+// ... of pw_group_kernel (no SEF form)
+#define PW_GROUP_TILES(X)                                                                                                                        \
+    X(128, 32, 4, 1, true, 32, 1, false, false) X(128, 32, 4, 1, true, 32, 3, false, false) X(64, 64, 2, 2, true, 32, 1, false, false)            \
+    X(128, 128, 2, 2, true, 32, 1, false, false) X(128, 128, 2, 2, true, 64, 1, false, false)                                                     \
+    X(64, 128, 2, 2, true, 32, 1, false, false) X(64, 128, 2, 2, true, 32, 3, false, false)                                                       \
+    X(128, 32, 4, 1, false, 32, 3, false, false) X(128, 32, 4, 1, false, 32, 3, false, true) X(64, 64, 2, 2, false, 32, 3, false, false)          \
+    X(64, 64, 2, 2, false, 32, 3, false, true) X(128, 96, 4, 1, false, 32, 3, false, false) X(128, 96, 4, 1, false, 32, 3, false, true)           \
+    X(128, 128, 2, 2, false, 32, 3, false, false) X(128, 128, 2, 2, false, 32, 3, false, true)                                                    \
+    X(64, 128, 2, 2, false, 32, 3, false, false) X(64, 128, 2, 2, false, 32, 3, false, true)
+constexpr long pw_tile_key(int bp, int bc, bool conv, int bk, int pf, bool sef, bool fk) {
+    return (((((long)bp * 1000 + bc) * 100 + bk) * 8 + pf) * 8) + (conv ? 4 : 0) + (sef ? 2 : 0) + (fk ? 1 : 0);
+}
+
+int launch_pw_tile(const PwArgs& a, const PwChoice& c, hipStream_t s) {
+    switch (pw_tile_key(c.bp, c.bc, c.conv, c.bk, c.pf, c.sef, c.fk)) {
+#define X(BP, BC, WP, WC, CONV, BK, PF, SEF, FK) case pw_tile_key(BP, BC, CONV, BK, PF, SEF, FK): return launch_tile<BP, BC, WP, WC, CONV, BK, PF, SEF, FK>(a, s);
+        PW_TILES(X)
+#undef X
+    }
+    dn_set_error("pointwise: no pw_kernel<%d,%d,..,%d,%d,%d,%d,%d>", c.bp, c.bc, (int)c.conv, c.bk, c.pf, (int)c.sef, (int)c.fk);
+    return DN_E_UNSUPPORTED;
+}
+
+// tools/tune_pw.py (dev build): one tile variant for every launch that has it, whatever the shape
+void pw_forced(const PwArgs& a, bool conv, PwChoice& c) {
+    static const int tile[7][2] = {{256, 32}, {128, 32}, {128, 64}, {64, 64}, {128, 128}, {64, 128}, {128, 96}};
+    if (g_pw_tile >= 1 && g_pw_tile <= (conv ? 6 : 7)) c = pw_tile(a, conv, tile[g_pw_tile - 1][0], tile[g_pw_tile - 1][1]);
+    if (g_pw_tile == 8 && !conv && a.wfrag) { c = PwChoice(); c.kernel = PwChoice::PW_XS; }
+}
+
 }  // namespace
 
-// All problems must be of the same kind (pointwise or implicit-GEMM conv); the tile is chosen for the widest one.
 int launch_pointwise_group(const PwArgs* arr, int count, bool conv, hipStream_t s) {
     DN_REQUIRE(count >= 1 && count <= 12, "pointwise group: %d problems", count);
-    int maxc = 0;
-    long wg128 = 0;
     for (int i = 0; i < count; ++i) {
         DN_REQUIRE(arr[i].cin % 8 == 0 && arr[i].m > 0, "pointwise group: bad problem %d", i);
         DN_REQUIRE(!conv || arr[i].cv_cin % 32 == 0, "conv group: cin=%d must be a multiple of 32", arr[i].cv_cin);
-        if (arr[i].cout > maxc) maxc = arr[i].cout;
-        wg128 += (long)dn_cdiv(arr[i].m, 128) * dn_cdiv(arr[i].cout, 128);
     }
-    if (maxc <= 32 && conv && wg128 < 256) return launch_group_cfg<128, 32, 4, 1, true, 32, 3>(arr, count, s);
-    if (maxc <= 32) return conv ? launch_group_cfg<128, 32, 4, 1, true>(arr, count, s) : launch_group_cfg<128, 32, 4, 1, false>(arr, count, s);
-    if (maxc <= 64) return conv ? launch_group_cfg<64, 64, 2, 2, true>(arr, count, s) : launch_group_cfg<64, 64, 2, 2, false>(arr, count, s);
-    if (wg128 >= 1500 && conv) {
-        // MFMA-bound dense-conv heads: 64-deep stages as in launch_cfg (half the barriers per MFMA)
-        const int bk64 = 1;
-        bool all64 = bk64 != 0;
-        for (int i = 0; i < count; ++i) all64 &= arr[i].cv_cin % 64 == 0;
-        if (all64) return launch_group_cfg<128, 128, 2, 2, true, 64>(arr, count, s);
+    const PwChoice c = pw_group_choose(arr, count, conv);
+    for (int i = 0; i < count; ++i)
+        if (const int rc = pw_check_honoured(arr[i], c, "pointwise group")) return rc;
+    switch (pw_tile_key(c.bp, c.bc, c.conv, c.bk, c.pf, c.sef, c.fk)) {
+#define X(BP, BC, WP, WC, CONV, BK, PF, SEF, FK) case pw_tile_key(BP, BC, CONV, BK, PF, SEF, FK): return launch_group_tile<BP, BC, WP, WC, CONV, BK, PF, FK>(arr, count, s);
+        PW_GROUP_TILES(X)
+#undef X
     }
-    if (wg128 >= 1500 && !conv) {
-        // 96-wide channel tiles (a wave = 32 pixels x 96 channels) where they pad less: the 546 class channels of the SSDLite heads are
-        // 6 x 96 = 576 columns instead of 5 x 128 = 640 -- the head launch is the longest full-chip launch of a forward (batch 64, three
-        // forwards in flight: 0.789 -> 0.775 ms; 128 x 192 tiles 0.808, 64 x 192 level)
-        double c96 = 0, c128 = 0;
-        for (int i = 0; i < count; ++i) {
-            c96 += (double)arr[i].m * dn_cdiv(arr[i].cout, 96) * 96;
-            c128 += (double)arr[i].m * dn_cdiv(arr[i].cout, 128) * 128;
-        }
-        if (c96 <= 0.95 * c128) return launch_group_cfg<128, 96, 4, 1, false>(arr, count, s);
-    }
-    if (wg128 >= 1500) return conv ? launch_group_cfg<128, 128, 2, 2, true>(arr, count, s) : launch_group_cfg<128, 128, 2, 2, false>(arr, count, s);
-    // the dense heads of the small levels (a few dozen workgroups, 72 - 144 K stages): latency-bound, stages requested 3 ahead
-    if (conv && wg128 < 256) return launch_group_cfg<64, 128, 2, 2, true, 32, 3>(arr, count, s);
-    return conv ? launch_group_cfg<64, 128, 2, 2, true>(arr, count, s) : launch_group_cfg<64, 128, 2, 2, false>(arr, count, s);
+    dn_set_error("pointwise group: no pw_group_kernel<%d,%d,..,%d,%d,%d,%d>", c.bp, c.bc, (int)c.conv, c.bk, c.pf, (int)c.fk);
+    return DN_E_UNSUPPORTED;
 }
 
-// the squeeze-excitation of a projection can be computed in the projection kernel's prologue (SEF variant of the 64 x 64 tile)
+// plan time: would the projection's launch fold the squeeze-excitation in (pw_choose, asked about the shape)
 bool pw_se_fold_supported(int cin, int cout, int squeeze, int hw) {
-    return dn_knob("DN_SE_FOLD", 1) != 0 && cin > 32 && cin <= 128 && cin % 8 == 0 && squeeze <= 32 && hw >= 64 &&
-           (cin < 256 || cout < 128);
+    static const float dummy_part = 0.f;
+    PwArgs q{};
+    q.sef_part = &dummy_part; q.sef_sq = squeeze; q.cin = cin; q.cout = cout; q.hw = hw; q.m = hw;
+    return pw_choose(q).sef;
 }
 
 int launch_pointwise(const PwArgs& a, hipStream_t s) {
@@ -1065,16 +976,17 @@ int launch_pointwise(const PwArgs& a, hipStream_t s) {
     DN_REQUIRE(a.cin % 8 == 0, "pointwise: cin=%d must be a multiple of 8", a.cin);
     DN_REQUIRE(a.out_fp32 || a.cout % 4 == 0, "pointwise: fp16 cout=%d must be a multiple of 4", a.cout);
     DN_REQUIRE(a.m > 0 && a.hw > 0, "pointwise: empty problem");
-    if (!g_pw_tile && pw_direct_supported(a)) return launch_pw_direct(a, s);
-    const int xs_mode = dn_knob("DN_PW_XS", 1);
-    if (g_pw_tile == 8 && a.wfrag) return launch_xs<32>(a, s);
-    if (xs_mode && !g_pw_tile && !a.sef_part && a.wfrag && a.cin % 16 == 0 && a.cin <= 1024 && a.cout <= 160 && !(a.act >> 8) &&      // (K % 16 == 8: measured slower than the tiled kernel)
-        ((a.cin >= 64 && a.m <= 8192) || (a.cin >= 160 && a.m <= 16384))) {
-        // measured (tools/tune_pw.py): the strip kernel wins where the tiled kernel cannot fill the chip -- M <= ~8k rows, or
-        // M <= ~16k rows when K is long (the tiled kernel pays one exposed round trip per 32-deep K stage)
-        return launch_xs<32>(a, s);
+    PwChoice c = pw_choose(a);
+    pw_forced(a, false, c);
+    if (const int rc = pw_check_honoured(a, c, "pointwise")) return rc;
+    switch (c.kernel) {
+        case PwChoice::PW_WSTAT: case PwChoice::PW_STREAM: case PwChoice::PW_DIRECT: return launch_pw_direct(a, c, s);
+        case PwChoice::PW_XS: return launch_xs<32>(a, s);
+        case PwChoice::PW_TILE: return launch_pw_tile(a, c, s);
+        default: break;
     }
-    return launch_select<false>(a, s);
+    dn_set_error("pointwise: no kernel for cin=%d cout=%d", a.cin, a.cout);
+    return DN_E_UNSUPPORTED;
 }
 
 PwArgs conv_to_pw(const ConvArgs& c) {
@@ -1095,31 +1007,11 @@ PwArgs conv_to_pw(const ConvArgs& c) {
 int launch_conv(const ConvArgs& c, hipStream_t s) {
     DN_REQUIRE(c.cin % 32 == 0, "conv: cin=%d must be a multiple of 32 (implicit-GEMM K stage within one tap)", c.cin);
     DN_REQUIRE(c.out_fp32 || c.cout % 4 == 0, "conv: fp16 cout=%d must be a multiple of 4", c.cout);
-    PwArgs a;
-    a.cv_k = c.k; a.cv_stride = c.stride; a.cv_pad = c.pad; a.cv_dil = c.dil; a.cv_h = c.h; a.cv_w = c.w_;
-    a.cv_ho = c.ho; a.cv_wo = c.wo; a.cv_cin = c.cin;
-    a.fd_cin32 = fastdiv((unsigned)(c.cin >> 5));
-    a.fd_k = fastdiv((unsigned)c.k);
-    a.x = c.x; a.w = c.w; a.bias = c.bias; a.residual = nullptr; a.se = nullptr; a.out = c.out; a.zeros = c.zeros;
-    a.hw = c.ho * c.wo;
-    a.m = c.n * a.hw;
-    a.cin = c.k * c.k * c.cin;
-    a.cout = c.cout; a.act = c.act; a.out_fp32 = c.out_fp32; a.out_img_stride = c.out_img_stride; a.out_base = c.out_base;
-    a.xq = c.xq;
+    const PwArgs a = conv_to_pw(c);
     DN_REQUIRE(a.m > 0, "conv: empty problem");
-    if (c.k == 1 && c.stride == 1 && c.pad == 0 && !c.out_fp32) {
-        // a 1x1 dense conv IS a pointwise conv: unless it is big enough for the 256 x 256-tile kernel, the pointwise path serves it
-        // (register-direct kernel up to cin = 256, 4-stage prefetch ring beyond; the implicit-GEMM body walks it one exposed stage at a time)
-        const long wg256 = (long)dn_cdiv(a.m, 256) * dn_cdiv(a.cout, 256);
-        if (!(dn_knob("DN_CONV_BIG", 1) && conv_big_supported(a) && wg256 >= 40)) {
-            PwArgs b;
-            b.x = c.x; b.w = c.w; b.bias = c.bias; b.residual = nullptr; b.se = nullptr; b.out = c.out;
-            b.hw = a.hw; b.m = a.m; b.cin = c.cin; b.cout = c.cout; b.act = c.act; b.out_fp32 = 0; b.out_img_stride = 0; b.out_base = 0;
-            b.xq = c.xq;
-            return launch_pointwise(b, s);
-        }
-    }
-    return launch_select<true>(a, s);
+    PwChoice ch = conv_choose(a, CONV_PLAIN);
+    if (ch.kernel == PwChoice::AS_POINTWISE) return launch_pointwise(conv_1x1_as_pw(a), s);
+    pw_forced(a, true, ch);
+    if (const int rc = pw_check_honoured(a, ch, "conv")) return rc;
+    return ch.kernel == PwChoice::PW_TILE ? launch_pw_tile(a, ch, s) : launch_conv_big(a, ch, s);
 }
-
-

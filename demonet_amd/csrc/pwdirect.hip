@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "choice.h"
 
 __device__ const uint4 g_pwdw_zero16 = {0u, 0u, 0u, 0u};      // what a tap outside the image reads
 
@@ -658,30 +659,6 @@ int launch_wstat_t(const PwArgs& a, hipStream_t s) {
     return DN_OK;
 }
 
-static bool pw_wstat_supported_(const PwArgs& a) {
-    return dn_knob("DN_PW_WSTAT", 1) != 0 && a.wfrag && !a.se && !a.residual && a.cin >= 16 && a.cin <= 128 && a.cin % 8 == 0 && a.m >= 3200 &&
-           (long)a.m * a.cout * 2 < 0x7fffffffL && a.cout >= 64;
-}
-
-static int launch_pw_wstat_(const PwArgs& a, hipStream_t s) {
-    const int ks1 = a.cin / 16 + 1, ctiles = dn_cdiv(a.cout, 32);
-    // tiles per run: as many as 96 registers of A fragments allow, least padding of the last run first
-    int rt = 2, waste = 1 << 30;
-    for (int c = 4; c >= 2; --c) {
-        if (ks1 * c > 24) continue;
-        const int w = dn_cdiv(ctiles, c) * c - ctiles;
-        if (w < waste) { waste = w; rt = c; }
-    }
-    switch (ks1 * 10 + rt) {
-#define DN_PWS_CASE(k, t) case k * 10 + t: return launch_wstat_t<k, t>(a, s);
-        DN_PWS_CASE(2, 2) DN_PWS_CASE(2, 3) DN_PWS_CASE(2, 4) DN_PWS_CASE(3, 2) DN_PWS_CASE(3, 3) DN_PWS_CASE(3, 4) DN_PWS_CASE(4, 2) DN_PWS_CASE(4, 3) DN_PWS_CASE(4, 4)
-        DN_PWS_CASE(5, 2) DN_PWS_CASE(5, 3) DN_PWS_CASE(5, 4) DN_PWS_CASE(6, 2) DN_PWS_CASE(6, 3) DN_PWS_CASE(6, 4) DN_PWS_CASE(7, 2) DN_PWS_CASE(7, 3)
-        DN_PWS_CASE(8, 2) DN_PWS_CASE(8, 3) DN_PWS_CASE(9, 2)
-#undef DN_PWS_CASE
-    }
-    return DN_E_UNSUPPORTED;
-}
-
 template <int KSF, int TC>
 int launch_t(const PwArgs& a, int wc_log, hipStream_t s) {
     const int BP = 32 * (4 >> wc_log), BC = (32 * TC) << wc_log;
@@ -715,52 +692,46 @@ int launch_pw_dw_direct(const PwArgs& a, const DwArgs& d, hipStream_t s) {
     return DN_OK;
 }
 
-bool pw_direct_supported(const PwArgs& a) {
-    // squeeze-excitation scaled inputs: only where a 32-row tile lies inside one image (the 40 x 40 maps) and the reduction is short
-    if (a.se && !(a.hw % 32 == 0 && a.cin <= 128)) return false;
-    return dn_knob("DN_PW_DIRECT", 1) != 0 && a.cv_k == 1 && !a.out_fp32 && !a.sef_part && !a.w_b && a.cin % 8 == 0 && a.cin >= 8 &&
-           a.cin <= 256 && a.cout % 8 == 0 && a.cout >= 8 && !(a.act >> 8) && a.out_img_stride == 0 && a.out_base == 0;
-}
-
-int launch_pw_direct(const PwArgs& a, hipStream_t s) {
-    DN_REQUIRE(pw_direct_supported(a), "pointwise (direct): unsupported cin=%d cout=%d", a.cin, a.cout);
-    // One 32-channel tile per wave (TC = 1) on the narrow layers: these launches are latency-bound, and twice the waves with half the
-    // registers overlap their single memory round trip better. Wide expansions (cout >= DN_PW_DIRECT_TC2, short reductions) take two
-    // tiles per wave: every wave re-reads its x rows once per channel tile, and at 21 tiles (112 -> 672) that is most of the traffic
-    // (measured: threshold 400 -> batch 64 1.115 -> 1.107 ms, batch 32 0.79 -> 0.77 ms; 200 and 600 in between).
-    // the expansions (short reduction, wide output, no scale, no residual): weight-stationary waves over LDS-DMA'd pixel tiles (round 6)
-    if (pw_wstat_supported_(a)) return launch_pw_wstat_(a, s);
+// the pwdirect.hip arms of launch_pointwise's switch (choice.h: pw_choose)
+int launch_pw_direct(const PwArgs& a, const PwChoice& c, hipStream_t s) {
     const int ctiles = dn_cdiv(a.cout, 32);
-    const int ksf = a.cin >> 4;
-    // wide expansions with enough rows: the streaming variant (pw_stream_kernel) -- channel runs sized so that all waves are resident at once
-    if (dn_knob("DN_PW_STREAM", 1) && !a.se && !a.residual && ksf >= 4 && ksf <= 8 && ctiles >= 12 && a.m >= 12800) {
-        const int px = 2;                   // 32-pixel tiles per wave
-        const long ptiles = dn_cdiv(a.m, 32 * px);
+    if (c.kernel == PwChoice::PW_WSTAT) {
+        switch (c.k * 10 + c.t) {
+#define DN_PWS_CASE(k, t) case k * 10 + t: return launch_wstat_t<k, t>(a, s);
+            DN_PWS_CASE(2, 2) DN_PWS_CASE(2, 3) DN_PWS_CASE(2, 4) DN_PWS_CASE(3, 2) DN_PWS_CASE(3, 3) DN_PWS_CASE(3, 4) DN_PWS_CASE(4, 2) DN_PWS_CASE(4, 3) DN_PWS_CASE(4, 4)
+            DN_PWS_CASE(5, 2) DN_PWS_CASE(5, 3) DN_PWS_CASE(5, 4) DN_PWS_CASE(6, 2) DN_PWS_CASE(6, 3) DN_PWS_CASE(6, 4) DN_PWS_CASE(7, 2) DN_PWS_CASE(7, 3)
+            DN_PWS_CASE(8, 2) DN_PWS_CASE(8, 3) DN_PWS_CASE(9, 2)
+#undef DN_PWS_CASE
+        }
+    } else if (c.kernel == PwChoice::PW_STREAM) {
+        // channel runs sized so that all waves are resident at once
+        const long ptiles = dn_cdiv(a.m, 32 * c.t);
         int runs = (int)std::max(1L, std::min((long)ctiles, (long)2800 / ptiles));
         const int per = dn_cdiv(ctiles, runs);
         runs = dn_cdiv(ctiles, per);
-        switch (ksf * 10 + px) {
+        switch (c.k * 10 + c.t) {
             case 42: return launch_stream_t<4, 2>(a, runs, per, s);
             case 52: return launch_stream_t<5, 2>(a, runs, per, s);
             case 62: return launch_stream_t<6, 2>(a, runs, per, s);
             case 72: return launch_stream_t<7, 2>(a, runs, per, s);
             case 82: return launch_stream_t<8, 2>(a, runs, per, s);
         }
-    }
-    if (ksf <= 8 && a.cout >= 400) {
+    } else if (c.kernel == PwChoice::PW_DIRECT && c.t == 2) {
         const int wc_log = ctiles <= 2 ? 0 : ctiles <= 4 ? 1 : 2;
-        switch (ksf) {
+        switch (c.k) {
 #define DN_PWD_CASE2(k) case k: return launch_t<k, 2>(a, wc_log, s);
             DN_PWD_CASE2(0) DN_PWD_CASE2(1) DN_PWD_CASE2(2) DN_PWD_CASE2(3) DN_PWD_CASE2(4) DN_PWD_CASE2(5) DN_PWD_CASE2(6) DN_PWD_CASE2(7) DN_PWD_CASE2(8)
 #undef DN_PWD_CASE2
         }
-    }
-    const int wc_log = ctiles <= 1 ? 0 : ctiles <= 2 ? 1 : 2;
-    switch (ksf) {
+    } else if (c.kernel == PwChoice::PW_DIRECT) {
+        const int wc_log = ctiles <= 1 ? 0 : ctiles <= 2 ? 1 : 2;
+        switch (c.k) {
 #define DN_PWD_CASE(k) case k: return launch_t<k, 1>(a, wc_log, s);
-        DN_PWD_CASE(0) DN_PWD_CASE(1) DN_PWD_CASE(2) DN_PWD_CASE(3) DN_PWD_CASE(4) DN_PWD_CASE(5) DN_PWD_CASE(6) DN_PWD_CASE(7) DN_PWD_CASE(8)
-        DN_PWD_CASE(9) DN_PWD_CASE(10) DN_PWD_CASE(11) DN_PWD_CASE(12) DN_PWD_CASE(13) DN_PWD_CASE(14) DN_PWD_CASE(15) DN_PWD_CASE(16)
+            DN_PWD_CASE(0) DN_PWD_CASE(1) DN_PWD_CASE(2) DN_PWD_CASE(3) DN_PWD_CASE(4) DN_PWD_CASE(5) DN_PWD_CASE(6) DN_PWD_CASE(7) DN_PWD_CASE(8)
+            DN_PWD_CASE(9) DN_PWD_CASE(10) DN_PWD_CASE(11) DN_PWD_CASE(12) DN_PWD_CASE(13) DN_PWD_CASE(14) DN_PWD_CASE(15) DN_PWD_CASE(16)
 #undef DN_PWD_CASE
+        }
     }
+    dn_set_error("pointwise (direct): no instantiation %d,%d for cin=%d cout=%d", c.k, c.t, a.cin, a.cout);
     return DN_E_UNSUPPORTED;
 }
