@@ -25,6 +25,20 @@ namespace {
 
 constexpr int GMAX = 256;       // ground-truth boxes per image held in LDS
 
+// torchvision.ops.boxes.box_iou of one (gt, anchor) pair, one rounding per operation as its separate torch ops round: rb - lt, clamp(min=0),
+// inter = w * h, union = (area1 + area2) - inter, inter / union (area1 = the gt's, area2 = the anchor's). Contracted to an fma the union
+// would see the unrounded product; on boxes that tie -- anchors that share a centre, an IoU of exactly the threshold -- that last bit
+// decides the match. The division is the correctly rounded fp32 sequence either way.
+__device__ __forceinline__ float match_iou(const float4 b, const float area_b, const float4 ab, const float area_ab) {
+#pragma clang fp contract(off)
+    const float w = fmaxf(fminf(b.z, ab.z) - fmaxf(b.x, ab.x), 0.f);
+    const float h = fmaxf(fminf(b.w, ab.w) - fmaxf(b.y, ab.y), 0.f);
+    const float inter = w * h;
+    const float both = area_b + area_ab;
+    const float uni = both - inter;
+    return inter / uni;
+}
+
 // ---- matching: one workgroup per image ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ssd_match_kernel(const float4* __restrict__ anchors, const float4* __restrict__ gt_boxes,
                                                        const int* __restrict__ gt_counts, int A, int gmax, float iou_thresh,
@@ -52,11 +66,7 @@ __global__ __launch_bounds__(256) void ssd_match_kernel(const float4* __restrict
         float best = -1.f;
         int best_g = 0;
         for (int g = 0; g < G; ++g) {
-            const float4 b = gb[g];
-            const float w = fmaxf(fminf(b.z, ab.z) - fmaxf(b.x, ab.x), 0.f);
-            const float h = fmaxf(fminf(b.w, ab.w) - fmaxf(b.y, ab.y), 0.f);
-            const float inter = w * h;
-            const float iou = inter / (ga[g] + aa - inter);
+            const float iou = match_iou(gb[g], ga[g], ab, aa);
             if (iou > best) { best = iou; best_g = g; }                 // max over dim 0: first maximum
             // IoU >= 0: its float bits order like the value. NaN (0 / 0 of two degenerate boxes) never wins a comparison.
             if (iou >= 0.f) atomicMax(&best_for_gt[g], ((unsigned long long)__float_as_uint(iou) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)a));
