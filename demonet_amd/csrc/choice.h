@@ -1,8 +1,10 @@
-// Which kernel a 1x1 convolution, a dense convolution or a grouped head launch runs on: ONE pure function per family (no HIP call, no label, argument
+// Which kernel a 1x1 convolution, a dense convolution, a grouped head launch, a depthwise convolution, the squeeze-excitation FCs or a stem runs on: ONE pure function per family (no HIP call, no label, argument
 // untouched; knobs read through dn_knob at the call -- INTEGRATION.md: kernel-choice knobs at every launch). The launchers validate, ask here and switch from
 // the answer to the template instantiation; the plan-time predicates ask the same functions about a shape. The order of the rules in a function is their
 // precedence, with the measurement that justifies a rule next to it; capability tests (*_shape, *_supported) stand in front of the function that uses them.
 #pragma once
+#include <algorithm>
+
 #include "common.h"
 
 struct PwChoice {
@@ -303,6 +305,85 @@ inline PwChoice pw_group_choose(const PwArgs* arr, int count, bool conv) {
         for (int i = 0; i < count; ++i)
             c.fk &= arr[i].cin % c.bk == 0 && !arr[i].se && !(arr[i].act >> 8) && (size_t)arr[i].m * arr[i].cin < (1u << 30) && (size_t)arr[i].cout * arr[i].cin < (1u << 30);
     }
+    return c;
+}
+
+// ================================================================ (d) one depthwise convolution (depthwise.hip: dw_kernel / dw_group_kernel<K, S, TW>)
+constexpr int dw_tw(int stride) { return stride == 1 ? 4 : 2; }     // output pixels of a row per thread: the window of TW pixels is (TW - 1) S + K input columns
+struct DwChoice {
+    enum Kernel { NONE, DW };
+    enum Pool { NO_POOL, POOLED, POOLED_SE };       // launch class: dw_kernel's POOL = 0, 1 (per-workgroup channel sums), 2 (+ the SE FCs in the image's last workgroup)
+    Kernel kernel = NONE;
+    int k = 0, stride = 0, tw = 0;
+    Pool pool = NO_POOL;
+};
+inline DwChoice dw_choose(const DwArgs& a) {
+    DwChoice c;
+    c.k = a.k; c.stride = a.stride;
+    if ((a.k != 3 && a.k != 5) || (a.stride != 1 && a.stride != 2)) return c;
+    c.kernel = DwChoice::DW; c.tw = dw_tw(a.stride);
+    c.pool = a.se_scale ? DwChoice::POOLED_SE : a.pool ? DwChoice::POOLED : DwChoice::NO_POOL;       // (the SE tail without a pooled output: the launcher refuses it)
+    return c;
+}
+
+// ================================================================ (e) the squeeze-excitation FCs
+// the small ones (the 40 x 40 blocks of MobileNetV3): DN_SE_SMALL moves them from the projection's prologue into the tail of the pooling depthwise launch
+// (plan.hip, both sites); the device's dw_se_tail_is_small adds what only the launch knows (constexpr: callable from there)
+constexpr bool se_is_small(int c, int squeeze) { return c <= 128 && squeeze <= 32; }
+struct SeChoice {
+    enum Kernel { FC, FC8_14_6, FC8_15_4 };     // se_fc_kernel, se_fc8_kernel<FB, PB>: 16-byte weight rows / partial rows in flight per thread
+    Kernel kernel = FC;
+    int rs = 0, ks1 = 0, ks2 = 0;               // se_fc8_kernel's slices of the partial rows and of the two reduction axes (they size its LDS)
+};
+inline SeChoice se_choose(int c, int squeeze, int nblk) {
+    SeChoice s;
+    if (!depthwise_se_tail_supported(c, squeeze) || !dn_knob("DN_SE_FC8", 1)) return s;      // 16-byte loads need both widths in whole 8s
+    s.rs = std::max(1, std::min(1024 / (c >> 2), nblk));
+    s.ks1 = std::max(1, std::min(1024 / (squeeze >> 3), c >> 3));
+    s.ks2 = std::max(1, std::min(1024 / (c >> 3), squeeze >> 3));
+    // the 960 / 240 blocks (29 - 30 rows per slice): two batches of 15 instead of three of 14
+    const bool wide = (dn_cdiv(c, s.ks1) > 14 || dn_cdiv(squeeze, s.ks2) > 14) && nblk <= 4 * s.rs;
+    s.kernel = wide ? SeChoice::FC8_15_4 : SeChoice::FC8_14_6;
+    return s;
+}
+
+// ================================================================ (f) the stem (3 x 3, 16 / 32 / 64 output channels)
+struct StemChoice {
+    enum Kernel { NONE, SPLIT, S2, MFMA64P, MFMA64, PLAIN };    // stem_split_kernel, stem3s2_kernel, stem_mfma64p_kernel, stem_mfma64_kernel, stem_kernel
+    Kernel kernel = NONE;
+    int tpw = 0, ahead = 0;     // SPLIT: tiles per wave, tiles a request runs ahead
+    bool touch = false;         // SPLIT: the wave touches its image lines up front
+};
+inline StemChoice stem_choose(const StemArgs& a) {
+    StemChoice c;
+    if (a.k != 3 || (a.cout != 16 && a.cout != 32 && a.cout != 64)) return c;
+    // the fp16 matrix cores with split operands: the three stems of the zoo, inside the kernel's 32-bit byte offsets
+    const bool split_inst = (a.cout == 64 && a.stride == 1 && a.act == DN_ACT_RELU) || (a.cout == 16 && a.stride == 2 && a.act == DN_ACT_HSWISH) ||
+                            (a.cout == 32 && a.stride == 2 && a.act == DN_ACT_RELU6);
+    const bool split_geom = a.stride == 1 ? (a.ho == a.h && a.wo == a.w_) : ((a.w_ & 1) == 0 && 2 * a.wo == a.w_ && a.ho == (a.h + 1) / 2);
+    if (a.pad == 1 && a.split_ok && dn_knob("DN_STEM_SPLIT", 1) && a.wo >= 32 && (long)3 * a.h * a.w_ < (1L << 28) && (long)a.ho * a.wo * a.cout < (1L << 29) &&
+        split_inst && split_geom) {
+        c.kernel = StemChoice::SPLIT;
+        // requests run 3 tiles ahead and the wave touches its lines up front for the 64-channel stem (1 GB of stores per forward: a first touch of an
+        // image line behind that stream outlasts two tiles; 16 images of 512 x 512, same box: 145 us -> 126 with the touch, 128 with 3 tiles
+        // ahead, 121 - 126 with both, 123 with 4), 2 tiles ahead and no touch for the narrow ones (17.6 / 36.3 us; with the touch 19.1 / 37.2).
+        c.ahead = a.cout >= 64 ? 3 : 2;
+        c.touch = a.cout >= 64;
+        // tiles per wave: 8 for the 64-channel stem (the weights' split -- 64 values per lane -- once per 8 tiles), 4 for the narrow ones (their
+        // launches are small: more, shorter waves; measured 4 / 8 / 16: 17.5 / 19.3 / 19.0 us for 16 channels, 36.2 / 38.0 / 38.4 for 32,
+        // 147.5 / 144.8 / 144.6 for 64)
+        c.tpw = a.cout >= 64 ? 8 : 4;
+        return c;
+    }
+    // fp32 from here on. 3 x 3 stride 2 on an even-width image: all nine (channel, row) loads up front
+    if (a.stride == 2 && a.pad == 1 && (a.w_ & 1) == 0 && 2 * a.wo == a.w_) { c.kernel = StemChoice::S2; return c; }
+    // 64 channels, stride 1 on the fp32 matrix cores; pipelined inside the wave where pad 1 / ReLU / "same" let the step run without branches
+    if (dn_knob("DN_STEM_MFMA", 1) && a.cout == 64 && a.stride == 1 && (long)3 * a.h * a.w_ < (1L << 30)) {
+        const bool pipe = dn_knob("DN_STEM_PIPE", 1) && a.pad == 1 && a.act == DN_ACT_RELU && a.ho == a.h && a.wo == a.w_ && a.wo >= 32 && (long)a.h * a.w_ < (1L << 24);
+        c.kernel = pipe ? StemChoice::MFMA64P : StemChoice::MFMA64;
+        return c;
+    }
+    c.kernel = StemChoice::PLAIN;
     return c;
 }
 

@@ -5,9 +5,7 @@
 //   transform.py:129-138 applied on load.
 // All of these are HBM-bound streaming kernels: NHWC fp16, 16-byte (8-channel) vectors per lane,
 // channel index fastest across lanes so every wave instruction touches whole 128-B lines, fp32 accumulation.
-#include <algorithm>
-
-#include "common.h"
+#include "choice.h"
 
 #ifdef DN_DEV_STAMPS
 static long long* g_se_stamps = nullptr;     // dev build only (tools/probe_se.py)
@@ -151,9 +149,10 @@ __device__ __forceinline__ void dw_se_tail_small(const DwArgs& a, const int n, c
     fc(w2, act2, j0, j1, z, ogp2, KS2, c, b2v, a.se_scale + (size_t)n * c, true);
 }
 // (dw_se_tail_small keeps TWO weight rows per thread and FC: the K slices of its thread map must be at most two rows long. c <= 128 and
-//  sq <= 32 imply that -- 256 / pow2(ceil(sq / 8)) >= 64 slices for fc1, >= 16 for fc2 -- and the condition is spelled out rather than implied.)
+//  sq <= 32 imply that -- 256 / pow2(ceil(sq / 8)) >= 64 slices for fc1, >= 16 for fc2 -- and the condition is spelled out rather than implied.
+//  se_is_small (choice.h) is the rule by which the plan sends an SE here: necessary on the host, not sufficient -- nblk is only known here.)
 __device__ __forceinline__ bool dw_se_tail_is_small(int c, int sq, int nblk) {
-    if (!(c <= 128 && sq <= 32 && nblk <= 32)) return false;
+    if (!(se_is_small(c, sq) && nblk <= 32)) return false;
     int ogp1 = 1, ogp2 = 1;
     while (ogp1 < ((sq + 7) >> 3)) ogp1 <<= 1;
     while (ogp2 < ((c + 7) >> 3)) ogp2 <<= 1;
@@ -163,8 +162,7 @@ __device__ __forceinline__ bool dw_se_tail_is_small(int c, int sq, int nblk) {
 
 // POOL: 0 = none, 1 = per-workgroup channel sums for the squeeze-excitation, 2 = sums + the FCs in the image's last workgroup
 //   (dw_se_tail: its 16-row load batches need 114 registers, which capped EVERY pooling launch while the code was compiled into all of them).
-// MODE bit 2: software-pipelined kernel rows (below); 0: the batched rows.
-template <int K, int S, int TW, int POOL, int MODE>
+template <int K, int S, int TW, int POOL>
 __device__ __forceinline__ void dw_body(const DwArgs& a, const int bx, const int nblocks, const int n) {
     constexpr int NIN = (TW - 1) * S + K;
     extern __shared__ float red[];            // [256][8], only when pooling
@@ -172,18 +170,9 @@ __device__ __forceinline__ void dw_body(const DwArgs& a, const int bx, const int
     const unsigned idx0 = bx * 256 + threadIdx.x;
     const unsigned q1 = fd_div(idx0, a.fd_c8);
     const unsigned cg = idx0 - q1 * C8;
-    // strip position q1 -> (output row, strip). Plain: row-major. Row blocks (rb_log2 > 0, DN_DW_RB): q1 walks down RB rows before it moves
-    // to the next strip, so the ~256 / C8 strip positions of a workgroup form a RB-row block whose input rows overlap -- the K-fold
-    // vertical re-read of every input row is then served by the CU's own L1 instead of L2.
-    unsigned oy, xs;
-    if (a.rb_log2 == 0) {
-        oy = fd_div(q1, a.fd_xs);
-        xs = q1 - oy * a.fd_xs.d;
-    } else {
-        const unsigned blk = fd_div(q1, a.fd_rbxs), within = q1 - blk * a.fd_rbxs.d;
-        xs = within >> a.rb_log2;
-        oy = (blk << a.rb_log2) + (within & ((1u << a.rb_log2) - 1u));
-    }
+    // strip position q1 -> (output row, strip), row-major
+    const unsigned oy = fd_div(q1, a.fd_xs);
+    const unsigned xs = q1 - oy * a.fd_xs.d;
     const bool valid = (int)oy < a.ho;
     if (!valid && POOL == 0) return;
     const int ox0 = xs * TW;
@@ -204,71 +193,39 @@ __device__ __forceinline__ void dw_body(const DwArgs& a, const int bx, const int
     const int ix0 = ox0 * S - a.pad;
     typedef const __attribute__((address_space(1))) half8* gp8;     // explicit global pointers: the selected pointer must not degrade to a flat load
     const gp8 zero = (gp8)(&g_dw_zero16);
-    // RP kernel rows are requested together before their first use: hipcc otherwise waits for each row's loads before
-    // issuing the next row's (vmcnt(0) per row), i.e. K dependent memory round trips per thread. 3x3 takes all rows at once;
-    // 5x5 two at a time (all five would need 260 VGPRs of staging).
-    constexpr int RP = (K == 3) ? 3 : 2;
+    // Software-pipelined rows: two register sets; row ky + 1 is requested BEFORE the multiply-adds of row ky are issued, so only the first row's
+    // round trip is exposed (hipcc otherwise waits for each row's loads before issuing the next row's: K dependent round trips per thread).
+    // Measured against the batched form (RP rows requested together, three exposed round trips for 5x5): 5x5 29 -> 25.7 us per 40 x 40 launch;
+    // 3x3 takes its three rows in one round trip either way, but two row sets instead of three are 127 registers instead of 140 -- 4 waves per
+    // SIMD: the head group 36.4 -> 33.8 us.
+    // (Round 2 - 3 also carried a ONE-row-at-a-time form, 70 - 116 registers: with it a forward's result depended on what else ran on the chip; cause not found in
+    //  two rounds of hunting (profiles/r03_dw_rows_hunt.txt), deleted in round 4 -- the poison test of tests/test_gpu_pipeline.py and the in-flight stress test guard what is left.)
     const half_t* const wbase = a.w + c0;
     const half_t* const xbase = a.x + (size_t)n * a.h * a.w_ * a.c + c0;
-    if constexpr ((MODE & 4) != 0) {
-        // Software-pipelined rows (MODE bit 2, DN_DW_PIPE): two register sets; row ky + 1 is requested BEFORE the multiply-adds of row ky
-        // are issued, so only the first row's round trip is exposed (the batched form exposes ceil(K / RP) of them: three for 5x5).
-        half8 wv[2][K];
-        half8 xin[2][NIN];
-        auto load_row = [&](const int ky, const int buf) {
-            const int iy = (int)oy * S - a.pad + ky;
-            const bool yok = iy >= 0 && iy < a.h;
+    half8 wv[2][K];
+    half8 xin[2][NIN];
+    auto load_row = [&](const int ky, const int buf) {
+        const int iy = (int)oy * S - a.pad + ky;
+        const bool yok = iy >= 0 && iy < a.h;
 #pragma unroll
-            for (int kx = 0; kx < K; ++kx) wv[buf][kx] = *reinterpret_cast<const half8*>(wbase + (unsigned)((ky * K + kx) * a.c));
-            const half_t* rowp = xbase + (unsigned)((yok ? iy : 0) * a.w_ * a.c);
+        for (int kx = 0; kx < K; ++kx) wv[buf][kx] = *reinterpret_cast<const half8*>(wbase + (unsigned)((ky * K + kx) * a.c));
+        const half_t* rowp = xbase + (unsigned)((yok ? iy : 0) * a.w_ * a.c);
 #pragma unroll
-            for (int i = 0; i < NIN; ++i) {
-                const int ix = ix0 + i;
-                const bool ok = yok && ix >= 0 && ix < a.w_;
-                xin[buf][i] = *(ok ? (gp8)(rowp + (unsigned)(ix * a.c)) : zero);
-            }
-        };
-        load_row(0, 0);
-#pragma unroll
-        for (int ky = 0; ky < K; ++ky) {
-            if (ky + 1 < K) load_row(ky + 1, (ky + 1) & 1);
-#pragma unroll
-            for (int t = 0; t < TW; ++t)
-#pragma unroll
-                for (int kx = 0; kx < K; ++kx)
-                    fma_mix_h8(acc[t], *reinterpret_cast<const uint4*>(&xin[ky & 1][t * S + kx]), *reinterpret_cast<const uint4*>(&wv[ky & 1][kx]));
+        for (int i = 0; i < NIN; ++i) {
+            const int ix = ix0 + i;
+            const bool ok = yok && ix >= 0 && ix < a.w_;
+            xin[buf][i] = *(ok ? (gp8)(rowp + (unsigned)(ix * a.c)) : zero);
         }
-    } else {
+    };
+    load_row(0, 0);
 #pragma unroll
-    for (int ky0 = 0; ky0 < K; ky0 += RP) {
-        half8 wv[RP][K];
-        half8 xin[RP][NIN];
+    for (int ky = 0; ky < K; ++ky) {
+        if (ky + 1 < K) load_row(ky + 1, (ky + 1) & 1);
 #pragma unroll
-        for (int rr = 0; rr < RP; ++rr) {
-            const int ky = ky0 + rr;
-            if (ky >= K) continue;
-            const int iy = (int)oy * S - a.pad + ky;
-            const bool yok = iy >= 0 && iy < a.h;
+        for (int t = 0; t < TW; ++t)
 #pragma unroll
-            for (int kx = 0; kx < K; ++kx) wv[rr][kx] = *reinterpret_cast<const half8*>(wbase + (unsigned)((ky * K + kx) * a.c));
-            const half_t* rowp = xbase + (unsigned)((yok ? iy : 0) * a.w_ * a.c);
-#pragma unroll
-            for (int i = 0; i < NIN; ++i) {
-                const int ix = ix0 + i;
-                const bool ok = yok && ix >= 0 && ix < a.w_;
-                xin[rr][i] = *(ok ? (gp8)(rowp + (unsigned)(ix * a.c)) : zero);
-            }
-        }
-#pragma unroll
-        for (int rr = 0; rr < RP; ++rr) {
-            if (ky0 + rr >= K) continue;
-#pragma unroll
-            for (int t = 0; t < TW; ++t)
-#pragma unroll
-                for (int kx = 0; kx < K; ++kx)
-                    fma_mix_h8(acc[t], *reinterpret_cast<const uint4*>(&xin[rr][t * S + kx]), *reinterpret_cast<const uint4*>(&wv[rr][kx]));
-        }
-    }
+            for (int kx = 0; kx < K; ++kx)
+                fma_mix_h8(acc[t], *reinterpret_cast<const uint4*>(&xin[ky & 1][t * S + kx]), *reinterpret_cast<const uint4*>(&wv[ky & 1][kx]));
     }
     half_t* orow = a.out + ((size_t)(n * a.ho + oy) * a.wo) * a.c + c0;
 #pragma unroll
@@ -334,11 +291,11 @@ __device__ __forceinline__ void dw_body(const DwArgs& a, const int bx, const int
     }
 }
 
-template <int K, int S, int TW, int POOL, int MODE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE & 4) ? (K == 3 ? 4 : 3) : 1))) void dw_kernel(DwArgs a, int nblocks) {
+template <int K, int S, int TW, int POOL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 3 ? 4 : 3))) void dw_kernel(DwArgs a, int nblocks) {
     int img, bx;
     if (!xcd_image_of2(a.xq, a.n, img, bx)) return;
-    dw_body<K, S, TW, POOL, MODE>(a, bx, nblocks, img);
+    dw_body<K, S, TW, POOL>(a, bx, nblocks, img);
 }
 
 // Grouped launch: up to 12 independent depthwise problems of the same (k, stride) and batch in ONE launch (the head
@@ -351,8 +308,8 @@ struct DwGroup {
     DwArgs a[12];
 };
 
-template <int K, int S, int TW, int MODE = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE & 4) && K == 3 ? 4 : 1))) void dw_group_kernel(DwGroup g) {
+template <int K, int S, int TW>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 3 ? 4 : 1))) void dw_group_kernel(DwGroup g) {
     int p = 0;
 #pragma unroll
     for (int i = 1; i < 12; ++i)
@@ -363,22 +320,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE & 4) 
     if (a.xq > 0) { img = (rel & 7) * a.xq + blockIdx.y; bx = rel >> 3; }
     else { img = blockIdx.y; bx = rel; }
     if (img >= a.n) return;
-    dw_body<K, S, TW, 0, MODE>(a, bx, g.nblocks[p], img);
+    dw_body<K, S, TW, 0>(a, bx, g.nblocks[p], img);
 }
 
-template <int K, int S, int TW>
-bool dw_fill(DwArgs& a) {
-    const unsigned c8 = a.c / 8, xs = (a.wo + TW - 1) / TW;
+// what the launcher fills in, and whether the problem lies inside the kernel's index range
+bool dw_fill(DwArgs& a, const int tw) {
+    const unsigned c8 = a.c / 8, xs = (a.wo + tw - 1) / tw;
     a.fd_c8 = fastdiv(c8);
     a.fd_xs = fastdiv(xs);
-    // row blocks: the largest power of two <= DN_DW_RB that divides the output height (the thread count, and with it the number of
-    // pooled partial rows the plan sized, stays what it is)
-    int rb = 0;
-    for (int want = 1; (2 << rb) <= want && a.ho % (2 << rb) == 0; ) ++rb;
-    a.rb_log2 = rb;
-    a.fd_rbxs = fastdiv(xs << rb);
     const unsigned long long threads = (unsigned long long)a.ho * xs * c8 + 256;
-    return fd_ok(threads, c8) && fd_ok(threads / c8 + 1, xs << rb) && (unsigned long long)a.h * a.w_ * a.c < 0x80000000ull;
+    return fd_ok(threads, c8) && fd_ok(threads / c8 + 1, xs) && (unsigned long long)a.h * a.w_ * a.c < 0x80000000ull;
+}
+int dw_blocks(const DwArgs& a, const int tw) { return dn_cdiv((long)a.ho * ((a.wo + tw - 1) / tw) * (a.c / 8), 256); }      // workgroups per image
+
+// DwChoice -> <K, S, TW>: the one table of instantiations (choice.h dw_choose admits exactly these; dw_tw states TW)
+template <int K_, int S_>
+struct DwInst { static constexpr int K = K_, S = S_, TW = dw_tw(S_); };
+template <class F>
+int dw_dispatch(const DwChoice& c, F&& f) {
+    if (c.k == 3 && c.stride == 1) return f(DwInst<3, 1>{});
+    if (c.k == 3 && c.stride == 2) return f(DwInst<3, 2>{});
+    if (c.k == 5 && c.stride == 1) return f(DwInst<5, 1>{});
+    if (c.k == 5 && c.stride == 2) return f(DwInst<5, 2>{});
+    dn_set_error("depthwise: unsupported k=%d stride=%d", c.k, c.stride);
+    return DN_E_UNSUPPORTED;
 }
 
 template <int K, int S, int TW>
@@ -388,48 +353,34 @@ int launch_dw_group(const DwArgs* arr, int count, hipStream_t s) {
     int acc = 0;
     for (int i = 0; i < count; ++i) {
         g.a[i] = arr[i];
-        DN_REQUIRE((dw_fill<K, S, TW>(g.a[i])), "depthwise group: problem %d outside the index range of the kernel", i);
-        DN_REQUIRE(!arr[i].pool && arr[i].n == arr[0].n && arr[i].xq == arr[0].xq, "depthwise group: problems must share the batch and have no pooled output");
+        DN_REQUIRE(dw_fill(g.a[i], TW), "depthwise group: problem %d outside the index range of the kernel", i);
         g.start[i] = acc;
-        g.nblocks[i] = dn_cdiv((long)arr[i].ho * ((arr[i].wo + TW - 1) / TW) * (arr[i].c / 8), 256);
+        g.nblocks[i] = dw_blocks(arr[i], TW);
         acc += g.nblocks[i] * (arr[i].xq > 0 ? 8 : 1);
     }
     g.start[count] = acc;
     dn_note_kernel("dw_group_kernel<%d,%d,%d>", K, S, TW);
-    hipLaunchKernelGGL((dw_group_kernel<K, S, TW, 4>), dim3(acc, arr[0].xq > 0 ? arr[0].xq : arr[0].n), dim3(256), 0, s, g);
+    hipLaunchKernelGGL((dw_group_kernel<K, S, TW>), dim3(acc, arr[0].xq > 0 ? arr[0].xq : arr[0].n), dim3(256), 0, s, g);
     return DN_OK;
 }
 
 template <int K, int S, int TW>
-int launch_dw(const DwArgs& a0, hipStream_t s) {
+int launch_dw(const DwArgs& a0, const DwChoice::Pool pool, hipStream_t s) {
     DwArgs a = a0;
-    DN_REQUIRE((dw_fill<K, S, TW>(a)), "depthwise: %d x %d x %d outside the index range of the kernel", a.ho, a.wo, a.c);
-    const long threads = (long)a.ho * ((a.wo + TW - 1) / TW) * (a.c / 8);       // per image
+    DN_REQUIRE(dw_fill(a, TW), "depthwise: %d x %d x %d outside the index range of the kernel", a.ho, a.wo, a.c);
     dn_note_kernel("dw_kernel<%d,%d,%d>", K, S, TW);
-    const int nblocks = dn_cdiv(threads, 256);
-    if (a.se_scale) DN_REQUIRE(a.pool && a.se_counter && depthwise_se_tail_supported(a.c, a.se_sq), "depthwise: squeeze-excitation tail needs the pooled output and c <= 1024, squeeze <= 256, both multiples of 8");
-    const size_t pool_lds = a.se_scale ? (size_t)(a.c + a.se_sq + 2048) * 4 : (size_t)256 * 8 * 4;
+    const int nblocks = dw_blocks(a, TW);
     const dim3 grid = xcd_grid2(nblocks, a.xq, a.n);
-    const int cls = a.pool ? (a.se_scale ? 4 : 2) : 1;      // launch class: 1 = no pooling, 2 = pooled sums, 4 = pooled sums + SE tail
-    // software-pipelined rows, default on, stress-tested. 5x5 (DN_DW_PIPE): one exposed round trip instead of three, 29 -> 25.7 us per 40 x 40 launch. 3x3 (DN_DW_PIPE3): the batched form already takes its three rows in one round trip, but two row sets instead of three are 127 registers instead of 140 -- 4 waves per SIMD: the head group 36.4 -> 33.8 us.
-    // (Round 2 - 3 also carried a ONE-row-at-a-time form, 70 - 116 registers: with it a forward's result depended on what else ran on the chip; cause not found in
-    //  two rounds of hunting (profiles/r03_dw_rows_hunt.txt), deleted in round 4 -- the poison test of tests/test_gpu_pipeline.py and the in-flight stress test guard what is left.)
-    const bool pipe = K == 5 ? (7 & cls) != 0 : (7 & cls) != 0;
-    const size_t lds = a.pool ? pool_lds : 0;
-    if (pipe) {
-        if (a.pool && a.se_scale) hipLaunchKernelGGL((dw_kernel<K, S, TW, 2, 4>), grid, dim3(256), lds, s, a, nblocks);
-        else if (a.pool) hipLaunchKernelGGL((dw_kernel<K, S, TW, 1, 4>), grid, dim3(256), lds, s, a, nblocks);
-        else hipLaunchKernelGGL((dw_kernel<K, S, TW, 0, 4>), grid, dim3(256), lds, s, a, nblocks);
-        return DN_OK;
+    switch (pool) {
+        case DwChoice::NO_POOL: hipLaunchKernelGGL((dw_kernel<K, S, TW, 0>), grid, dim3(256), 0, s, a, nblocks); break;
+        case DwChoice::POOLED: hipLaunchKernelGGL((dw_kernel<K, S, TW, 1>), grid, dim3(256), (size_t)256 * 8 * 4, s, a, nblocks); break;
+        case DwChoice::POOLED_SE:
+            DN_REQUIRE(a.pool && a.se_counter && depthwise_se_tail_supported(a.c, a.se_sq), "depthwise: squeeze-excitation tail needs the pooled output and c <= 1024, squeeze <= 256, both multiples of 8");
+            hipLaunchKernelGGL((dw_kernel<K, S, TW, 2>), grid, dim3(256), (size_t)(a.c + a.se_sq + 2048) * 4, s, a, nblocks);
+            break;
     }
-    if (a.pool && a.se_scale) hipLaunchKernelGGL((dw_kernel<K, S, TW, 2, 0>), grid, dim3(256), lds, s, a, nblocks);
-    else if (a.pool) hipLaunchKernelGGL((dw_kernel<K, S, TW, 1, 0>), grid, dim3(256), lds, s, a, nblocks);
-    else hipLaunchKernelGGL((dw_kernel<K, S, TW, 0, 0>), grid, dim3(256), lds, s, a, nblocks);
     return DN_OK;
 }
-
-template <int K, int S, int TW>
-int dw_blocks(const DwArgs& a) { return dn_cdiv((long)a.ho * ((a.wo + TW - 1) / TW) * (a.c / 8), 256); }
 
 // ---- SE FCs: (sum of partials)/pixels -> fc1(+b) -> ReLU -> fc2(+b) -> Hardsigmoid   (mobilenetv3.py:31-36) ------------
 // One 1024-thread workgroup per image. Both weight matrices are stored TRANSPOSED and in fp16 at plan time (w1t [c][sq], w2t [sq][c];
@@ -749,8 +700,9 @@ __global__ __launch_bounds__(1024) void se_fc8_kernel(const float* __restrict__ 
 // One thread per output pixel, all COUT channels. The weights are wave-uniform: indexing the kernel-argument pointer
 // with compile-time offsets makes hipcc fetch them with s_load (scalar cache) and feed them as SGPR operands of
 // v_fmac -- no LDS, no 400-register weight image (the first version needed 256 VGPRs and spilled for COUT >= 32).
-template <int COUT, int K>
+template <int COUT>
 __global__ __launch_bounds__(256) void stem_kernel(StemArgs a, int nblocks) {
+    constexpr int K = 3;
     const float* __restrict__ wts = a.w;
     const float* __restrict__ bias = a.bias;
     if (a.zero_u32 && blockIdx.x == 0)       // the chain's squeeze-excitation counters (DwArgs::se_counter): cleared once per forward, ahead of every pooling launch
@@ -1314,89 +1266,27 @@ __global__ __launch_bounds__(256) void stem_split_kernel(StemArgs a, int nblocks
     }
 }
 
-template <int COUT, int K>
-int launch_stem_t(const StemArgs& a, hipStream_t s) {
-    const int images = a.xq > 0 ? 8 * a.xq : a.n;      // image slots of the launch (XCD grouping: 8 groups of xq)
-    if (K == 3 && a.pad == 1 && a.split_ok && dn_knob("DN_STEM_SPLIT", 1) && a.wo >= 32 && (long)3 * a.h * a.w_ < (1L << 28) &&
-        (long)a.ho * a.wo * COUT < (1L << 29)) {
-        // requests run 3 tiles ahead and the wave touches its lines up front for the 64-channel stem (1 GB of stores per forward: a first touch of an
-        // image line behind that stream outlasts two tiles; 16 images of 512 x 512, same box: 145 us -> 126 with the touch, 128 with 3 tiles
-        // ahead, 121 - 126 with both, 123 with 4), 2 tiles ahead and no touch for the narrow ones (17.6 / 36.3 us; with the touch 19.1 / 37.2).
-        // tiles per wave: 8 for the 64-channel stem (the weights' split -- 64 values per lane -- once per 8 tiles), 4 for the narrow ones (their
-        // launches are small: more, shorter waves; measured 4 / 8 / 16: 17.5 / 19.3 / 19.0 us for 16 channels, 36.2 / 38.0 / 38.4 for 32,
-        // 147.5 / 144.8 / 144.6 for 64)
-        constexpr int TPW = COUT >= 64 ? 8 : 4;
-        const int nv = a.stride == 1 ? 30 : 31;
-        const int tiles = dn_cdiv((long)a.ho * a.wo, nv);
-        const int nblocks = dn_cdiv(tiles, 4 * TPW);
-        const dim3 grid(nblocks * images);
-#define DN_STEM_SPLIT_CASE(C, S_, ACT_)                                                                                                    \
-        if (COUT == C && a.stride == S_ && a.act == ACT_ && (S_ == 1 ? (a.ho == a.h && a.wo == a.w_) : ((a.w_ & 1) == 0 && 2 * a.wo == a.w_ && a.ho == (a.h + 1) / 2))) { \
-            dn_note_kernel("stem_split_kernel<%d,%d>", C, S_);                                                                             \
-            hipLaunchKernelGGL((stem_split_kernel<C, S_, ACT_, (C >= 64 ? 8 : 4), (C >= 64 ? 3 : 2), (C >= 64)>), grid, dim3(256), 0, s, a, nblocks); \
-            return DN_OK;                                                                                                                  \
-        }
-        DN_STEM_SPLIT_CASE(64, 1, DN_ACT_RELU)
-        DN_STEM_SPLIT_CASE(16, 2, DN_ACT_HSWISH)
-        DN_STEM_SPLIT_CASE(32, 2, DN_ACT_RELU6)
-#undef DN_STEM_SPLIT_CASE
-    }
-    if (K == 3 && a.stride == 2 && a.pad == 1 && (a.w_ & 1) == 0 && 2 * a.wo == a.w_) {
-        dn_note_kernel("stem3s2_kernel<%d>", COUT);
-        const int nblocks = dn_cdiv((long)a.ho * a.wo, 256);
-        hipLaunchKernelGGL((stem3s2_kernel<COUT>), dim3(nblocks * images), dim3(256), 0, s, a, nblocks);
-        return DN_OK;
-    }
-    const int mf = dn_knob("DN_STEM_MFMA", 1);
-    if (mf && K == 3 && COUT == 64 && a.stride == 1 && (long)3 * a.h * a.w_ < (1L << 30)) {
-        const int tiles = dn_cdiv((long)a.ho * a.wo, 32), per_wave = 8;
-        if (dn_knob("DN_STEM_PIPE", 1) && a.pad == 1 && a.act == DN_ACT_RELU && a.ho == a.h && a.wo == a.w_ && a.wo >= 32 && (long)a.h * a.w_ < (1L << 24)) {
-            dn_note_kernel("stem_mfma64p_kernel");
-            const int nblocks = dn_cdiv(tiles, 4 * per_wave);
-            hipLaunchKernelGGL((stem_mfma64p_kernel<8>), dim3(nblocks * images), dim3(256), 0, s, a, nblocks);
-            return DN_OK;
-        }
-        dn_note_kernel("stem_mfma64_kernel");
-        const int nblocks = dn_cdiv(tiles, 4 * per_wave);
-        hipLaunchKernelGGL(stem_mfma64_kernel, dim3(nblocks * images), dim3(256), 0, s, a, tiles, per_wave, nblocks);
-        return DN_OK;
-    }
-    dn_note_kernel("stem_kernel<%d,%d>", COUT, K);
-    const int nblocks = dn_cdiv((long)a.ho * a.wo, 256);
-    hipLaunchKernelGGL((stem_kernel<COUT, K>), dim3(nblocks * images), dim3(256), 0, s, a, nblocks);
-    return DN_OK;
-}
-
 }  // namespace
 
 int launch_depthwise(const DwArgs& a, hipStream_t s) {
     DN_REQUIRE(a.c % 8 == 0, "depthwise: c=%d must be a multiple of 8", a.c);
     DN_REQUIRE(!a.pool || a.c / 8 <= 256, "depthwise: pooled channel groups %d > 256", a.c / 8);
-    if (a.k == 3 && a.stride == 1) return launch_dw<3, 1, 4>(a, s);
-    if (a.k == 3 && a.stride == 2) return launch_dw<3, 2, 2>(a, s);
-    if (a.k == 5 && a.stride == 1) return launch_dw<5, 1, 4>(a, s);
-    if (a.k == 5 && a.stride == 2) return launch_dw<5, 2, 2>(a, s);
-    dn_set_error("depthwise: unsupported k=%d stride=%d", a.k, a.stride);
-    return DN_E_UNSUPPORTED;
+    const DwChoice c = dw_choose(a);
+    return dw_dispatch(c, [&](auto i) { using I = decltype(i); return launch_dw<I::K, I::S, I::TW>(a, c.pool, s); });
 }
 
 int launch_depthwise_group(const DwArgs* arr, int count, hipStream_t s) {
     DN_REQUIRE(count >= 1 && count <= 12, "depthwise group: %d problems", count);
     for (int i = 0; i < count; ++i) {
-        DN_REQUIRE(arr[i].c % 8 == 0 && !arr[i].pool && arr[i].k == arr[0].k && arr[i].stride == arr[0].stride && arr[i].n == arr[0].n,
-                   "depthwise group: problem %d is not compatible", i);
+        DN_REQUIRE(arr[i].c % 8 == 0 && !arr[i].pool && arr[i].k == arr[0].k && arr[i].stride == arr[0].stride && arr[i].n == arr[0].n &&
+                   arr[i].xq == arr[0].xq, "depthwise group: problem %d is not compatible (one k, stride and batch, no pooled output)", i);
     }
-    if (arr[0].k == 3 && arr[0].stride == 1) return launch_dw_group<3, 1, 4>(arr, count, s);
-    if (arr[0].k == 3 && arr[0].stride == 2) return launch_dw_group<3, 2, 2>(arr, count, s);
-    if (arr[0].k == 5 && arr[0].stride == 1) return launch_dw_group<5, 1, 4>(arr, count, s);
-    return launch_dw_group<5, 2, 2>(arr, count, s);
+    return dw_dispatch(dw_choose(arr[0]), [&](auto i) { using I = decltype(i); return launch_dw_group<I::K, I::S, I::TW>(arr, count, s); });
 }
 
 int depthwise_pool_blocks(const DwArgs& a) {
-    if (a.k == 3 && a.stride == 1) return dw_blocks<3, 1, 4>(a);
-    if (a.k == 3 && a.stride == 2) return dw_blocks<3, 2, 2>(a);
-    if (a.k == 5 && a.stride == 1) return dw_blocks<5, 1, 4>(a);
-    return dw_blocks<5, 2, 2>(a);
+    const DwChoice c = dw_choose(a);
+    return c.kernel == DwChoice::NONE ? 0 : dw_blocks(a, c.tw);      // (0: no kernel, the launch itself is refused)
 }
 
 bool depthwise_se_tail_supported(int c, int squeeze) { return c % 8 == 0 && squeeze % 8 == 0 && c <= 1024 && squeeze <= 256 && c >= 8 && squeeze >= 8; }
@@ -1404,14 +1294,11 @@ bool depthwise_se_tail_supported(int c, int squeeze) { return c % 8 == 0 && sque
 int launch_se_fc(const float* partial, int nblk, const void* w1t, const float* b1, const void* w2t, const float* b2, float* scale,
                  int n, int c, int squeeze, int pool_pixels, hipStream_t s, int xq) {
     DN_REQUIRE(c <= 1024 && squeeze <= 256 && c % 2 == 0 && squeeze % 2 == 0, "se: c=%d squeeze=%d outside the kernel's range (even, <= 1024 / 256)", c, squeeze);
-    if (c % 8 == 0 && squeeze % 8 == 0 && c >= 8 && squeeze >= 8 && dn_knob("DN_SE_FC8", 1)) {
-        const int C4 = c >> 2, RS = std::max(1, std::min(1024 / C4, nblk));
-        const int KS1 = std::max(1, std::min(1024 / (squeeze >> 3), c >> 3)), KS2 = std::max(1, std::min(1024 / (c >> 3), squeeze >> 3));
-        const size_t pf = (size_t)std::max(std::max(RS * c, KS1 * squeeze), KS2 * c);
+    const SeChoice ch = se_choose(c, squeeze, nblk);
+    if (ch.kernel != SeChoice::FC) {
+        const size_t pf = (size_t)std::max(std::max(ch.rs * c, ch.ks1 * squeeze), ch.ks2 * c);
         dn_note_kernel("se_fc8_kernel");
-        const int per1 = dn_cdiv(c, KS1), per2 = dn_cdiv(squeeze, KS2);
-        const bool wide = (per1 > 14 || per2 > 14) && nblk <= 4 * RS;          // two batches of 15 instead of three of 14
-        auto k = wide ? se_fc8_kernel<15, 4> : se_fc8_kernel<14, 6>;
+        auto k = ch.kernel == SeChoice::FC8_15_4 ? se_fc8_kernel<15, 4> : se_fc8_kernel<14, 6>;
         hipLaunchKernelGGL(k, dim3(xq > 0 ? 8 * xq : n), dim3(1024), (size_t)(c + squeeze + pf) * sizeof(float), s, partial, nblk,
                            reinterpret_cast<const half_t*>(w1t), b1, reinterpret_cast<const half_t*>(w2t), b2, scale, c, squeeze,
                            1.0f / (float)pool_pixels, g_se_stamps, n, xq, 5);
@@ -1425,9 +1312,38 @@ int launch_se_fc(const float* partial, int nblk, const void* w1t, const float* b
 }
 
 int launch_stem(const StemArgs& a, hipStream_t s) {
-    if (a.k == 3 && a.cout == 16) return launch_stem_t<16, 3>(a, s);
-    if (a.k == 3 && a.cout == 32) return launch_stem_t<32, 3>(a, s);
-    if (a.k == 3 && a.cout == 64) return launch_stem_t<64, 3>(a, s);
+    const StemChoice c = stem_choose(a);
+    const int images = a.xq > 0 ? 8 * a.xq : a.n;      // image slots of the launch (XCD grouping: 8 groups of xq)
+    const long px = (long)a.ho * a.wo;
+    const int per256 = dn_cdiv(px, 256), tiles32 = dn_cdiv(px, 32);
+    auto go = [&](int nblocks, auto kernel, auto... extra) {       // nblocks: workgroups per image
+        hipLaunchKernelGGL(kernel, dim3(nblocks * images), dim3(256), 0, s, a, extra..., nblocks);
+        return DN_OK;
+    };
+    switch (c.kernel) {
+        case StemChoice::SPLIT: {
+            const int nb = dn_cdiv(dn_cdiv(px, a.stride == 1 ? 30 : 31), 4 * c.tpw);      // tiles of 30 / 31 output pixels, tpw per wave
+            auto is = [&](int cout, int tpw, int ahead, bool touch) { return a.cout == cout && c.tpw == tpw && c.ahead == ahead && c.touch == touch; };
+            dn_note_kernel("stem_split_kernel<%d,%d>", a.cout, a.stride);
+            if (is(64, 8, 3, true)) return go(nb, stem_split_kernel<64, 1, DN_ACT_RELU, 8, 3, true>);
+            if (is(16, 4, 2, false)) return go(nb, stem_split_kernel<16, 2, DN_ACT_HSWISH, 4, 2, false>);
+            if (is(32, 4, 2, false)) return go(nb, stem_split_kernel<32, 2, DN_ACT_RELU6, 4, 2, false>);
+            break;
+        }
+        case StemChoice::S2:
+            dn_note_kernel("stem3s2_kernel<%d>", a.cout);
+            return a.cout == 16 ? go(per256, stem3s2_kernel<16>) : a.cout == 32 ? go(per256, stem3s2_kernel<32>) : go(per256, stem3s2_kernel<64>);
+        case StemChoice::MFMA64P:       // (both: 8 tiles of 32 pixels per wave)
+            dn_note_kernel("stem_mfma64p_kernel");
+            return go(dn_cdiv(tiles32, 4 * 8), stem_mfma64p_kernel<8>);
+        case StemChoice::MFMA64:
+            dn_note_kernel("stem_mfma64_kernel");
+            return go(dn_cdiv(tiles32, 4 * 8), stem_mfma64_kernel, tiles32, 8);
+        case StemChoice::PLAIN:
+            dn_note_kernel("stem_kernel<%d,%d>", a.cout, 3);
+            return a.cout == 16 ? go(per256, stem_kernel<16>) : a.cout == 32 ? go(per256, stem_kernel<32>) : go(per256, stem_kernel<64>);
+        case StemChoice::NONE: break;
+    }
     dn_set_error("stem: unsupported k=%d cout=%d", a.k, a.cout);
     return DN_E_UNSUPPORTED;
 }

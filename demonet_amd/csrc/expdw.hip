@@ -762,9 +762,9 @@ int launch_t(const ExpDwArgs& a0, hipStream_t s) {
     // split the 64-channel chunks over grid.y until there are enough workgroups to fill the chip a few times over
     // (not with a project stage: it sums over all chunks inside the workgroup)
     const int tiles_x = dn_cdiv(a.Wo, OW), tiles_y = dn_cdiv(a.Ho, OH), tiles = tiles_x * tiles_y, chunks = dn_cdiv(a.cexp, 64);
-    const int want = 1024;
+    const int min_wgs = 1024;
     int cpw = chunks;
-    while (!proj && cpw > 1 && (long)tiles * a.n * dn_cdiv(chunks, cpw) < want) --cpw;
+    while (!proj && cpw > 1 && (long)tiles * a.n * dn_cdiv(chunks, cpw) < min_wgs) --cpw;
     a.chunks_per_wg = cpw;
     {   // dev: DN_EXPDW_STAMP_SEL = 10 * H + stride stamps only the launches of that shape (every launch writes the same buffer)
         const int sel = g_xd_stamps ? dn_knob("DN_EXPDW_STAMP_SEL", 0) : 0;

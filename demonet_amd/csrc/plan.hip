@@ -14,7 +14,7 @@
 #include <tuple>
 #include <vector>
 
-#include "common.h"
+#include "choice.h"
 
 // ---------------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -449,7 +449,7 @@ static void fold_se_into_projections(const dn_plan* p, OpLaunches& at) {
         if (users == 1 && pw_se_fold_supported(pj.cin, pj.cout, so.squeeze, ti.h * ti.w)) {
             // DN_SE_SMALL (default 1, see below): these small FCs go to the tail of the pooling depthwise launch instead and the projection runs
             // on the register-direct kernel with the scale applied to its x fragments
-            if (se_small && (ti.h * ti.w) % 32 == 0 && pj.cin <= 128 && depthwise_se_tail_supported(so.cin, so.squeeze)) continue;
+            if (se_small && (ti.h * ti.w) % 32 == 0 && se_is_small(pj.cin, so.squeeze) && depthwise_se_tail_supported(so.cin, so.squeeze)) continue;
             at[i].se_host = i + 1;
             at[i + 1].se = i;
         }
@@ -473,7 +473,7 @@ static void se_in_depthwise_tails(dn_plan* p, OpLaunches& at) {
     for (int i = 1; i < (int)p->ops.size(); ++i) {
         const dn_op_desc& so = p->ops[i];
         if (so.type != DN_OP_SE || at[i].se_host >= 0) continue;
-        if (!all && !(so.cin <= 128 && so.squeeze <= 32)) continue;      // DN_SE_SMALL alone: the small ones only
+        if (!all && !se_is_small(so.cin, so.squeeze)) continue;      // DN_SE_SMALL alone: the small ones only
         int j = -1;
         for (int q = 0; q < i; ++q) if (p->ops[q].type == DN_OP_DW && p->ops[q].pool == so.in) j = q;
         if (j < 1 || !depthwise_se_tail_supported(so.cin, so.squeeze) || !plain(at, j)) continue;
@@ -497,7 +497,6 @@ static void size_pool_partials(dn_plan* p, const OpLaunches& at) {
         }
         DwArgs a{};
         a.n = 1; a.h = ti.h; a.w_ = ti.w; a.c = o.cin; a.k = o.k; a.stride = o.stride; a.pad = o.pad; a.ho = to.h; a.wo = to.w;
-        a.pool = reinterpret_cast<float*>(1);      // (geometry only: a pooling launch)
         p->pool_blocks[o.pool] = depthwise_pool_blocks(a);
     }
 }
@@ -804,7 +803,6 @@ static DwArgs make_dw(const Ctx& c, const dn_op_desc& o) {
     a.n = c.n; a.h = ti.h; a.w_ = ti.w; a.c = o.cin; a.k = o.k; a.stride = o.stride; a.pad = o.pad; a.act = o.act;
     a.ho = to.h; a.wo = to.w;
     a.pool = o.pool >= 0 ? c.t<float>(o.pool) : nullptr;
-    a.pool_rows = o.pool >= 0 ? c.p->pool_blocks[o.pool] : 0;
     a.xq = c.xq;
     return a;
 }

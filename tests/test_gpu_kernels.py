@@ -275,6 +275,17 @@ def test_bad_arguments_report_errors():
     x = torch.zeros(8, 12, dtype=torch.half, device="cuda")
     rc = lib.dn_pointwise_conv(_ptr(x), _ptr(x), None, _ptr(x), None, None, _ptr(x), 8, 12, 8, 8, 0, 0, 0, None)
     assert rc < 0 and b"multiple of 8" in lib.dn_last_error()
+    # a depthwise (k, stride) without an instantiation is refused, never run as another size: 7 x 7 on n 1, 9 x 9, c 8
+    xd = torch.randn(1, 9, 9, 8).half().cuda()
+    wd = torch.randn(49, 8).half().cuda()
+    bd = torch.zeros(8, device="cuda")
+    out = torch.full((1, 9, 9, 8), 7.0, dtype=torch.half, device="cuda")
+    rc = lib.dn_depthwise_conv(_ptr(xd), _ptr(wd), _ptr(bd), _ptr(out), 1, 9, 9, 8, 7, 1, 3, 0,
+                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    err = lib.dn_last_error()
+    torch.cuda.synchronize()
+    assert rc == -4 and b"k=7" in err and b"stride=1" in err          # DN_E_UNSUPPORTED
+    assert bool((out == 7.0).all())
 
 
 EXPDW_CASES = [
