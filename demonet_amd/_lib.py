@@ -8,6 +8,7 @@ DN_ABI_VERSION = 1
 
 DN_OP = dict(stem=1, pw=2, dw=3, se=4, conv=5, maxpool=6, l2norm=7)
 DN_T = dict(act=0, image=1, vec=2, pool=3)
+DN_NMS = dict(hard=0, linear=1, gaussian=2)
 
 
 class TensorDesc(C.Structure):
@@ -53,6 +54,10 @@ _SIGNATURES = {
     "dn_postprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                  C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dn_postprocess_soft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                      C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dn_set_nms": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "dn_pointwise_conv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "dn_depthwise_conv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -389,6 +389,7 @@ struct PostArgs {
     HistRows hrows;
     int small_first = -1;       // with scores_ready: first anchor still in logit form (the levels below 32 pixels per image); -1 / A: none
     unsigned* tickets = nullptr; // with small levels: one zeroed counter per image (left at zero) -> the cut-off runs in the last softmax tile of the image, no tau launch
+    int nms_method = DN_NMS_HARD; float nms_sigma = 0.5f;     // DN_NMS_*: the soft modes decay scores in the per-class reduce (no cut-off, no fast path); sigma: Gaussian only
 };
 // where launch_postprocess keeps its arrays inside the workspace it is given (the fused head launch writes the first three itself)
 struct PostBuffers {

@@ -154,6 +154,8 @@ struct dn_plan {
     hipEvent_t ev_fork = nullptr, ev_branch[3] = {nullptr, nullptr, nullptr};
     std::map<std::pair<int, int>, Layout> sub_layouts;
     int chains_override = 0;                // dn_set_chains: > 0 = that many sub-batch chains per forward whatever the batch size
+    int nms_method = DN_NMS_HARD;           // dn_set_nms: the per-class reduce of the next forwards' post-process
+    float nms_sigma = 0.5f;
     float* packed_out = nullptr;            // dn_set_packed_output: what the next forwards copy into Call::packed
     std::vector<Launch> launches;           // the forward's kernel launches in order (dn_create), covering every op once
     int n_se_in_dw = 0;                     // depthwise launches computing an SE in their tail; slot q of the counter block belongs to the q-th
@@ -676,6 +678,18 @@ extern "C" int dn_set_chains(dn_plan* p, int chains) {
     drop_graphs(p);
     p->layouts.clear();
     p->sub_layouts.clear();
+    return DN_OK;
+}
+
+extern "C" int dn_set_nms(dn_plan* p, int method, float sigma) {
+    DN_REQUIRE(p, "null plan");
+    DN_REQUIRE(method == DN_NMS_HARD || method == DN_NMS_SOFT_LINEAR || method == DN_NMS_SOFT_GAUSSIAN, "dn_set_nms: unknown method %d", method);
+    DN_REQUIRE(method != DN_NMS_SOFT_GAUSSIAN || (std::isfinite(sigma) && sigma > 0.f), "dn_set_nms: Gaussian soft-NMS needs a finite sigma > 0");
+    DN_REQUIRE(p->in_call.load() == 0, "dn_set_nms: the plan is inside a forward of another host thread");
+    if (method == p->nms_method && sigma == p->nms_sigma) return DN_OK;
+    p->nms_method = method;
+    p->nms_sigma = sigma;
+    drop_graphs(p);      // the captured launch sequences hold the other method's kernels
     return DN_OK;
 }
 
@@ -1212,6 +1226,7 @@ static int enqueue(dn_plan* p, const Call& call, const Layout& L, hipStream_t s,
         a.score_thresh = d.score_thresh; a.nms_thresh = d.nms_thresh; a.topk = d.topk_candidates; a.dets = d.detections_per_img;
         a.boxes = call.boxes; a.scores = call.scores; a.labels = call.labels; a.counts = call.counts; a.kept_anchor = nullptr;
         a.packed = call.packed;
+        a.nms_method = p->nms_method; a.nms_sigma = p->nms_sigma;
         a.ws = ws + L.post_off; a.ws_bytes = L.post_bytes;
         a.xq = c.xq;
         a.scores_ready = ep.scores_ready; a.hrows = ep.rows; a.small_first = ep.small_first;
@@ -1471,10 +1486,10 @@ extern "C" size_t dn_postprocess_workspace_bytes(int n, int num_anchors, int num
     return postprocess_ws_bytes(n, num_anchors, num_classes, topk, dets);
 }
 
-extern "C" int dn_postprocess(const float* logits, const float* reg, const float* anchors, int n, int A, int K, float image_h,
-                              float image_w, const float* scale_xy, float score_thresh, float nms_thresh, int topk, int dets,
-                              float* boxes, float* scores, int64_t* labels, int32_t* counts, int32_t* kept_anchor, void* ws,
-                              size_t ws_bytes, void* stream) {
+extern "C" int dn_postprocess_soft(const float* logits, const float* reg, const float* anchors, int n, int A, int K, float image_h,
+                                   float image_w, const float* scale_xy, float score_thresh, float nms_thresh, int nms_method, float nms_sigma,
+                                   int topk, int dets, float* boxes, float* scores, int64_t* labels, int32_t* counts, int32_t* kept_anchor,
+                                   void* ws, size_t ws_bytes, void* stream) {
     DN_REQUIRE(logits && reg && anchors && boxes && scores && labels && counts && ws, "dn_postprocess: null argument");
     DN_REQUIRE(score_thresh >= 0.f, "dn_postprocess: score_thresh must be >= 0");
     if (K > DN_MAX_CLASSES) {
@@ -1485,10 +1500,19 @@ extern "C" int dn_postprocess(const float* logits, const float* reg, const float
     a.logits = logits; a.reg = reg; a.anchors = anchors; a.n = n; a.A = A; a.K = K;
     a.img_h = image_h; a.img_w = image_w; a.scale_xy = scale_xy;
     a.score_thresh = score_thresh; a.nms_thresh = nms_thresh; a.topk = topk; a.dets = dets;
+    a.nms_method = nms_method; a.nms_sigma = nms_sigma;
     a.boxes = boxes; a.scores = scores; a.labels = labels; a.counts = counts; a.kept_anchor = kept_anchor;
     a.ws = ws; a.ws_bytes = ws_bytes;
     a.xq = xcd_images_per_group(n);
     return launch_postprocess(a, reinterpret_cast<hipStream_t>(stream), nullptr);
+}
+
+extern "C" int dn_postprocess(const float* logits, const float* reg, const float* anchors, int n, int A, int K, float image_h,
+                              float image_w, const float* scale_xy, float score_thresh, float nms_thresh, int topk, int dets,
+                              float* boxes, float* scores, int64_t* labels, int32_t* counts, int32_t* kept_anchor, void* ws,
+                              size_t ws_bytes, void* stream) {
+    return dn_postprocess_soft(logits, reg, anchors, n, A, K, image_h, image_w, scale_xy, score_thresh, nms_thresh, DN_NMS_HARD, 0.f, topk, dets,
+                               boxes, scores, labels, counts, kept_anchor, ws, ws_bytes, stream);
 }
 
 extern "C" int dn_pointwise_conv(const void* x, const void* w, const void* w_frag, const float* bias, const void* residual,

@@ -7,6 +7,7 @@ into the HIP library through the C ABI (include/demonet_hip.h). There is no PyTo
 library or without a GPU the forward raises.
 """
 import ctypes as C
+import math
 from collections import OrderedDict
 from typing import Dict, List, Optional
 
@@ -132,6 +133,7 @@ class SSD(_Tracked):
         self._packed_set = -1         # address the plan's dn_set_packed_output setting holds (-1: unknown): _set_packed
         self._fast_sig = None         # _remember_weights
         self._graph_mode = None       # set_graph_mode; None: never asked, the library's default (DN_GRAPH) holds
+        self.nms_method, self.nms_sigma = "hard", 0.5      # set_nms
         self._plan_gen = 0            # counts the plans built (a new plan may reuse the old one's address: pipelines compare this)
         self._pipe_refs, self._pipe_chains = 0, None      # open ForwardPipelines of the current plan, and the `chains` they share
         self._feat_gen = 0            # counts the forwards that wrote this model's workspaces (a head backward checks its features are still there)
@@ -205,6 +207,8 @@ class SSD(_Tracked):
         with torch.cuda.device(device):
             self._lowered = LoweredModel(self.graph, sd)
             self._handle = self._lowered.create()
+        if self.nms_method != "hard":
+            self._apply_nms(self.nms_method, self.nms_sigma)
         self._sig = sig
         self._remember_weights(device)
         self._bufs = {}
@@ -230,6 +234,31 @@ class SSD(_Tracked):
         self._graph_mode = bool(enabled)
         if self._handle is not None:
             _lib.check(_lib.lib().dn_set_graph_mode(C.c_void_p(self._handle), int(enabled)))
+
+    def set_nms(self, method: str = "hard", sigma: float = 0.5):
+        """The per-class reduce of the post-process: "hard" (the reference's NMS, the default), or soft-NMS (Bodla et al., 2017) with
+        "linear" (a box overlapping an emitted one by IoU u > nms_thresh keeps 1 - u of its score) or "gaussian" (exp(-u^2 / sigma) of it)
+        decay; the scores returned are the decayed ones (include/demonet_hip.h, dn_set_nms). Plan state: every forward of this model
+        (forward, forward_batch, forward_uint8, the packed output, a ForwardPipeline) follows it from the next call on, the plan is not
+        rebuilt, and a rebuilt plan inherits it. Call it with no forward in flight. Returns self.
+        ValueError for an unknown method or a sigma that is not a finite number > 0 -- for every method, stricter than the C ABI, which
+        reads sigma in Gaussian mode only: the attribute always holds a value that a later switch to "gaussian" can use. A call that
+        fails, here or in the library, leaves the model's setting as it was."""
+        if not isinstance(method, str) or method not in _lib.DN_NMS:
+            raise ValueError("set_nms: method must be one of {}, got {!r}".format(sorted(_lib.DN_NMS), method))
+        try:
+            sigma = float(sigma)
+        except (TypeError, ValueError):
+            raise ValueError("set_nms: sigma must be a number, got {!r}".format(sigma)) from None
+        if not (math.isfinite(sigma) and sigma > 0.0):
+            raise ValueError("set_nms: sigma must be finite and > 0, got {!r}".format(sigma))
+        if self._handle is not None:
+            self._apply_nms(method, sigma)      # (raises when the library refuses: the attributes then still describe the plan)
+        self.nms_method, self.nms_sigma = method, sigma
+        return self
+
+    def _apply_nms(self, method, sigma):
+        _lib.check(_lib.lib().dn_set_nms(C.c_void_p(self._handle), _lib.DN_NMS[method], sigma), "dn_set_nms")
 
     def _buffers_for(self, n, h, w, device):
         key = (n, h, w, str(device))

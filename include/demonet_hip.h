@@ -140,6 +140,26 @@ DN_API int dn_postprocess(const float* cls_logits_dev, const float* bbox_regress
                    float* boxes_dev, float* scores_dev, int64_t* labels_dev, int32_t* counts_dev,
                    int32_t* kept_anchor_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Soft-NMS (Bodla et al., 2017) as the per-class reduce, instead of hard NMS. Per image and class, on the same candidates (score > score_thresh,
+ * the topk_candidates best): repeatedly emit the remaining candidate with the largest CURRENT score (ties: lower anchor index) and multiply the
+ * score of every other remaining candidate by f(u), u = its fp32 IoU with the emitted box:
+ *   DN_NMS_SOFT_LINEAR   f = u > nms_thresh ? 1 - u : 1
+ *   DN_NMS_SOFT_GAUSSIAN f = expf(-(u * u) / sigma)      (nms_thresh unused)
+ * a candidate whose score falls to score_thresh or below is dropped. The global top-D then ranks the decayed scores, which are the scores reported.
+ * Deterministic. The soft modes run every class of every image (the cut-off of the hard path does not hold under decay). */
+enum { DN_NMS_HARD = 0, DN_NMS_SOFT_LINEAR = 1, DN_NMS_SOFT_GAUSSIAN = 2 };
+/* The NMS method of the plan's later dn_forward / dn_forward_u8 (default DN_NMS_HARD; sigma is read by DN_NMS_SOFT_GAUSSIAN only and must then be
+ * finite and > 0). DN_E_INVALID for an unknown method or such a sigma. Like dn_set_chains it drops the cached graphs: call it with no forward of
+ * this plan in flight. dn_workspace_bytes does not change. */
+DN_API int dn_set_nms(dn_plan* plan, int method, float sigma);
+/* dn_postprocess with the method as an argument; DN_NMS_HARD is dn_postprocess bit for bit. Same workspace (dn_postprocess_workspace_bytes). */
+DN_API int dn_postprocess_soft(const float* cls_logits_dev, const float* bbox_regression_dev, const float* anchors_dev,
+                   int n, int num_anchors, int num_classes,
+                   float image_h, float image_w, const float* scale_xy_dev /* [n][2] (w,h) ratios or NULL */,
+                   float score_thresh, float nms_thresh, int nms_method, float nms_sigma, int topk_candidates, int detections_per_img,
+                   float* boxes_dev, float* scores_dev, int64_t* labels_dev, int32_t* counts_dev,
+                   int32_t* kept_anchor_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Single-kernel entry points (unit parity tests, micro-benchmarks, roofline measurement).
  * x: [m][cin] fp16 (NHWC rows), w: [cout][cin] fp16, bias fp32 [cout], residual [m][cout] fp16 or NULL,
  * w_frag (optional): the same weights in MFMA-fragment order (dn_op_desc PW w2) -- enables the strip kernel,
