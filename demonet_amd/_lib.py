@@ -9,6 +9,7 @@ DN_ABI_VERSION = 1
 DN_OP = dict(stem=1, pw=2, dw=3, se=4, conv=5, maxpool=6, l2norm=7)
 DN_T = dict(act=0, image=1, vec=2, pool=3)
 DN_NMS = dict(hard=0, linear=1, gaussian=2)
+DN_MERGE = dict(iou=0, ios=1)
 
 
 class TensorDesc(C.Structure):
@@ -82,6 +83,10 @@ _SIGNATURES = {
     "dn_forward_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dn_lite_head_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
     "dn_lite_head_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_int64] + [C.c_int] * 5 + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
+    "dn_crop_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dn_merge_detections_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "dn_merge_detections": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 6
+                            + [C.c_size_t, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -363,6 +363,21 @@ class SSD(_Tracked):
             _lib.check(_lib.lib().dn_forward_u8(*forward_args(handle, images.data_ptr(), n, h, w, b["outs"], b["ws"], stream)), "dn_forward_u8")
         return b["outs"]
 
+    def detect_sliced(self, images, tile=None, overlap: float = 0.25, full_image: bool = True, merge_thresh: Optional[float] = None,
+                      metric: str = "iou", class_agnostic: bool = False, max_tiles_per_forward: int = 64) -> List[Dict[str, Tensor]]:
+        """Sliced inference for images much larger than the network size (demonet_amd/sliced.py): the detector runs on overlapping
+        tiles at native resolution -- and, with full_image, on the whole image as well, which keeps the objects larger than a tile -- and the
+        per-tile detections, shifted into image coordinates, are merged by one more hard NMS on the device (include/demonet_hip.h,
+        dn_merge_detections: IoU or "ios" = intersection over the smaller box, threshold merge_thresh, per class or class_agnostic).
+        images: one [3, H, W] float tensor in [0, 1] on the GPU or a list of them (sizes may differ). tile: an int or (th, tw); default: the
+        network size, so tiles are not resized at all (tile_grid: stride tile - round(overlap * tile), the last tile of a row / column clamped
+        into the image). merge_thresh defaults to nms_thresh. The tiles of an image go through forward_batch in sub-batches of at most
+        max_tiles_per_forward; the NMS mode of set_nms applies inside each tile. Eval mode only.
+        Returns one {"boxes", "scores", "labels"} per image like forward, in image coordinates, at most detections_per_img each.
+        ValueError for bad arguments and for an image with more tiles than the merge takes (1 024 sources, 65 536 sources x detections_per_img)."""
+        from .sliced import detect_sliced
+        return detect_sliced(self, images, tile, overlap, full_image, merge_thresh, metric, class_agnostic, max_tiles_per_forward)
+
     def batch_split(self, n: int) -> int:
         """Number of parallel sub-batch launch chains a forward of n images is issued as (1 = a single chain)."""
         if self._handle is None:

@@ -274,6 +274,43 @@ DN_API int dn_lite_head_backward(const void* x_dev, const void* wd_dev, const fl
                                  int64_t dy_img_stride, int n, int h, int w, int c, int cout, float* g_wd_dev, float* g_bd_dev,
                                  float* g_w1_dev, float* g_b1_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Sliced inference (csrc/sliced.hip): detection on images much larger than the network size by overlapping tiles at native resolution. A caller
+ * crops the tiles (dn_crop_tiles), runs them as one dn_forward batch -- and, optionally, the whole image as one more forward -- and merges the
+ * per-tile results into image coordinates (dn_merge_detections). demonet_amd/sliced.py and SSD.detect_sliced are that caller.
+ *
+ * dn_crop_tiles: image_dev [3][h][w] fp32, origins_dev [t][2] int32 (x0, y0) ON THE DEVICE, out_dev [t][3][th][tw] fp32 contiguous = the images_dev
+ * of dn_forward with (n, h, w) = (t, th, tw). One gather launch, bit for bit; tiles whose rows start on 16-byte boundaries in both arrays (w, tw
+ * and x0 multiples of 4, aligned bases) move in 16-byte accesses, others as single floats. DN_E_INVALID for a null pointer, a non-positive size,
+ * t > 65535 and for a tile that leaves the image: to refuse that one, THIS CALL READS THE ORIGINS BACK (8 t bytes) AND WAITS FOR `stream` before it
+ * enqueues the launch -- the exception to this header's rule; it cannot be captured into a graph. */
+DN_API int dn_crop_tiles(const float* image_dev, int h, int w, const int32_t* origins_dev, int t, int th, int tw, float* out_dev, void* stream);
+
+/* Hard NMS over detections that already exist: s_total sources, each one image's worth of dn_forward output (boxes [S][d][4] fp32, scores [S][d]
+ * fp32, labels [S][d] int64, counts [S] int32), offsets_dev [S][2] fp32 (ox, oy) = where the source's origin lies in its output image, and the HOST
+ * array group_begin [groups + 1] int32: sources group_begin[g] .. group_begin[g + 1] - 1 form output image g (0 <= group_begin[0], non-decreasing,
+ * group_begin[groups] <= s_total; sources outside every group are ignored). Per group:
+ *   1. candidates: the rows j < counts[s] of its sources, without those whose score is NaN; the row order inside a source is not assumed;
+ *   2. a candidate's box is (x1 + ox, y1 + oy, x2 + ox, y2 + oy), one fp32 addition each; score and label unchanged;
+ *   3. rank: score descending, ties by ascending flattened index s * d + j;
+ *   4. in rank order, a candidate is kept unless a kept candidate of higher rank with the same label (any label when class_agnostic = 1) has
+ *      m > thresh with it (strict), m in fp32 in the operation order of the per-class NMS: area = (x2 - x1) * (y2 - y1),
+ *      inter = max(0, min x2 - max x1) * max(0, min y2 - max y1), DN_MERGE_IOU: m = inter / (a_i + a_j - inter), DN_MERGE_IOS (intersection over
+ *      the smaller box, which also removes a box nested in a large one): m = inter / min(a_i, a_j); a NaN m does not suppress;
+ *   5. the first d_out kept candidates, in rank order, are the output.
+ * Outputs: boxes_out [groups][d_out][4], scores_out [groups][d_out], labels_out [groups][d_out] int64, counts_out [groups] int32 and, optional
+ * (may be NULL), src_out [groups][d_out] int32 = the flattened index s * d + j the detection came from; rows at or beyond the count are zero (src -1).
+ * Limits: d and d_out 1 .. 512, at most 1 024 sources and 65 536 slots (sources * d) per group, s_total * d < 2^31: DN_E_UNSUPPORTED beyond them.
+ * DN_E_WORKSPACE below dn_merge_detections_workspace_bytes (which is 0 for sizes the call refuses; `groups` does not enter today). DN_E_INVALID for
+ * null pointers, non-positive sizes, an unknown metric, a NaN thresh, a group_begin that decreases or leaves 0 .. s_total, boxes / boxes_out /
+ * workspace not 16-byte aligned, offsets / labels not 8-byte aligned. group_begin is read during the call only. Asynchronous on `stream`, no host
+ * synchronisation, can be captured; deterministic (the same bits on every run). */
+enum { DN_MERGE_IOU = 0, DN_MERGE_IOS = 1 };
+DN_API size_t dn_merge_detections_workspace_bytes(int s_total, int d, int groups);
+DN_API int dn_merge_detections(const float* boxes_dev, const float* scores_dev, const int64_t* labels_dev, const int32_t* counts_dev,
+                               const float* offsets_dev, int s_total, int d, const int32_t* group_begin, int groups, int metric, float thresh,
+                               int class_agnostic, int d_out, float* boxes_out_dev, float* scores_out_dev, int64_t* labels_out_dev,
+                               int32_t* counts_out_dev, int32_t* src_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
