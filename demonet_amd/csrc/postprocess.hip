@@ -1292,7 +1292,8 @@ int launch_p2_fast(const PostArgs& a, const float* scoresT, const float4* boxes,
 
 }  // namespace
 
-// (tests/test_soft_nms.py reads scoresT and boxes back through this layout -- _post_soft(want_inputs=True): keep the two in step)
+// (tests/post_select_ref.py workspace_layout is the Python copy of this layout -- the tests read scoresT, boxes, keptCount, tauKey and needFull
+//  back through it: keep the two in step)
 PostBuffers post_buffers(void* ws, int n, int A, int K, int topk) {
     const size_t Km1 = K - 1;
     PostBuffers b;
@@ -1343,6 +1344,8 @@ int launch_postprocess(const PostArgs& a0, hipStream_t s, hipEvent_t* ev) {
     DN_REQUIRE(a.n > 0 && a.A > 0 && a.K >= 2, "postprocess: bad sizes n=%d A=%d K=%d", a.n, a.A, a.K);
     DN_REQUIRE(a.topk >= 1 && a.topk <= 512, "postprocess: topk_candidates=%d outside [1,512]", a.topk);
     DN_REQUIRE(a.dets >= 1 && a.dets <= 512, "postprocess: detections_per_img=%d outside [1,512]", a.dets);
+    // (score_thresh >= 0 here: dn_postprocess* and dn_create refuse a negative one -- a candidate's key is its score's bits and key 0 means "not
+    //  passing" (select_candidates), so a score that underflowed to exactly 0.0, which the reference keeps under a negative threshold, could not be one)
     if (a.K > DN_MAX_CLASSES) {
         dn_set_error("postprocess: num_classes=%d above the limit of %d (DN_MAX_CLASSES, background included)", a.K, DN_MAX_CLASSES);
         return DN_E_UNSUPPORTED;

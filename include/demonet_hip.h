@@ -131,7 +131,10 @@ DN_API int dn_forward_features(dn_plan* plan, const float* images_dev, int n, in
 /* Post-process only, replacing SSD.postprocess_detections (generalized_ssd.py:351-397) + transform.postprocess:
  * softmax -> decode (BoxCoder weights 10,10,5,5) -> clip -> per-class score>thr & top-k -> hard NMS (IoU > thr)
  * -> global top-D by score.  kept_anchor_dev (optional, may be NULL): [n][D] int32 anchor index per detection.
- * num_classes (background included) 2 .. DN_MAX_CLASSES: DN_E_UNSUPPORTED above; topk_candidates and detections_per_img 1 .. 512. */
+ * num_classes (background included) 2 .. DN_MAX_CLASSES: DN_E_UNSUPPORTED above; topk_candidates and detections_per_img 1 .. 512.
+ * score_thresh >= 0: dn_postprocess and dn_postprocess_soft return DN_E_INVALID for a negative threshold, and dn_create refuses a plan with
+ * one. The reference keeps a score that underflowed to exactly 0.0 under a negative threshold; here a zero score never is a candidate (its
+ * key, 0, means "not passing"), and a threshold of 0 already keeps every positive score. */
 DN_API size_t dn_postprocess_workspace_bytes(int n, int num_anchors, int num_classes, int topk_candidates, int detections_per_img);
 DN_API int dn_postprocess(const float* cls_logits_dev, const float* bbox_regression_dev, const float* anchors_dev,
                    int n, int num_anchors, int num_classes,

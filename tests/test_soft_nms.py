@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import post_select_ref as psr
 import soft_nms_ref as sr
 import ssd_oracle as so
 from demonet_amd import _lib, models, synth
@@ -213,14 +214,9 @@ def _post_soft(logits, reg, anchors, st, nt, method, sigma, topk, dets, ws_bytes
     outs = tuple(t.cpu().numpy() for t in (boxes, scores, labels, counts, kept))
     if not want_inputs or rc != 0:
         return rc, outs
-    # what the reduce worked on, left behind in the workspace (csrc/postprocess.hip post_buffers: the class-major scores [n][K-1][A] first, then
-    # the decoded boxes [n][A][4] at the next multiple of 256 bytes), in the oracle's form: softmax [A, K] (background column unused), boxes [A, 4]
-    nsc = n * (K - 1) * A * 4
-    off = (nsc + 255) // 256 * 256
-    sc = ws[:nsc].view(torch.float32).view(n, K - 1, A).cpu().numpy()
-    bx = ws[off:off + n * A * 16].view(torch.float32).view(n, A, 4).cpu().numpy()
-    inter = [(np.ascontiguousarray(np.concatenate([np.zeros((A, 1), np.float32), sc[i].T], 1)), bx[i]) for i in range(n)]
-    return rc, outs, inter
+    # what the reduce worked on, left behind in the workspace, in the oracle's form: softmax [A, K] (background column unused), boxes [A, 4]
+    # (tests/post_select_ref.py holds the one Python copy of csrc/postprocess.hip's post_buffers)
+    return rc, outs, psr.read_workspace(ws.cpu().numpy(), n, A, K, topk)["inter"]
 
 
 def _check_case(case, method, sigma):
