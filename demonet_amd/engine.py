@@ -6,7 +6,8 @@ host, `{image_id: output}` into the evaluator (engine.py:84-100). Here the same 
 while the host converts the previous ones: same `{image_id: {"boxes", "scores", "labels"}}` records (host tensors), same order.
 The COCO evaluator itself (pycocotools, `data/coco_eval.py`) is third-party and absent here; `evalrec.coco_detection_records`
 turns the records into the list `CocoEvaluator.prepare_for_coco_detection` builds (data/coco_eval.py:76-98) and
-`evalrec.voc_mean_ap` scores them the PASCAL VOC way.
+`evalrec.voc_mean_ap` scores them the PASCAL VOC way. `evaluate_voc` is the same loop with the scoring on the device: the detections stay
+there and only the mAP comes back (demonet_amd/voceval.py).
 """
 import collections
 import time
@@ -81,6 +82,73 @@ def evaluate(model, data_loader: Iterable, device="cuda:0", depth: int = 3) -> T
     model_time += time.perf_counter() - t0
     dt = time.perf_counter() - t_start
     return results, {"images": n_images, "seconds": dt, "images_per_sec": n_images / max(dt, 1e-9), "model_seconds": model_time}
+
+
+@torch.no_grad()
+def evaluate_voc(model, data_loader: Iterable, device="cuda:0", depth: int = 3, thresholds=(0.5,), use_07_metric: bool = False,
+                 pixel_offset: float = 1.0) -> Tuple[dict, Dict[str, float]]:
+    """PASCAL VOC mAP of `model` over `data_loader` with the detections left on the device. The loop is `evaluate`'s; the targets
+    hold the reference's `boxes` [k, 4] xyxy, `labels` [k] and, optionally, `difficult` [k] (num_classes is the model's). A batch's detections
+    never reach the host: once its slot is about to be reused, the current stream waits for the forward (`pipe.wait`) and
+    `voceval.VocAccumulator.update` marks true and false positives there, on the slot's own output tensors (`pipe.outputs`), and keeps copies
+    of scores, labels and flags on the device; the next submit on that slot orders itself behind the current stream. A batch of mixed sizes
+    is run by `model(images)` after the pipeline has drained and padded to [n][detections_per_img]. Only `summarize` waits for the device.
+    Returns (VocAccumulator.summarize(use_07_metric), stats) with the stats keys of `evaluate`; "seconds" includes the summary."""
+    from .voceval import VocAccumulator
+    device = torch.device(device)
+    model.eval()
+    acc = VocAccumulator(model.graph.num_classes, thresholds, pixel_offset)
+    pending = collections.deque()
+    pipe = None
+    shape = None
+    n_images = 0
+    model_time = 0.0
+
+    def collect(ticket, targets):
+        pipe.wait(ticket)                                                   # the current stream waits; the host does not
+        acc.update(*pipe.outputs(ticket), targets)
+
+    def drain():
+        while pending:
+            collect(*pending.popleft())
+
+    t_start = time.perf_counter()
+    for images, targets in data_loader:
+        same = isinstance(images, torch.Tensor) or len({tuple(im.shape) for im in images}) == 1
+        t0 = time.perf_counter()
+        if same:
+            batch = images if isinstance(images, torch.Tensor) else torch.stack(list(images))
+            batch = batch.to(device, non_blocking=True)
+            if pipe is None or tuple(batch.shape) != shape:
+                drain()
+                if pipe is not None:
+                    pipe.close()
+                shape = tuple(batch.shape)
+                pipe = ForwardPipeline(model, shape[0], height=shape[2], width=shape[3], depth=depth, device=device)
+            if len(pending) == depth:                                       # its slot is about to be reused
+                collect(*pending.popleft())
+            pending.append((pipe.submit(batch), targets))
+        else:
+            drain()
+            outputs = model([im.to(device) for im in images])
+            n, D = len(outputs), model.detections_per_img
+            boxes = torch.zeros((n, D, 4), dtype=torch.float32, device=device)
+            scores = torch.zeros((n, D), dtype=torch.float32, device=device)
+            labels = torch.zeros((n, D), dtype=torch.int64, device=device)
+            lens = [int(o["scores"].shape[0]) for o in outputs]
+            for i, (o, c) in enumerate(zip(outputs, lens)):
+                boxes[i, :c], scores[i, :c], labels[i, :c] = o["boxes"], o["scores"], o["labels"]
+            acc.update(boxes, scores, labels, torch.tensor(lens, dtype=torch.int32).to(device), targets)
+        model_time += time.perf_counter() - t0
+        n_images += len(targets)
+    t0 = time.perf_counter()
+    drain()
+    if pipe is not None:
+        pipe.close()
+    model_time += time.perf_counter() - t0
+    summary = acc.summarize(use_07_metric)
+    dt = time.perf_counter() - t_start
+    return summary, {"images": n_images, "seconds": dt, "images_per_sec": n_images / max(dt, 1e-9), "model_seconds": model_time}
 
 
 def coco_records(results: Dict[int, Dict[str, torch.Tensor]]) -> List[dict]:

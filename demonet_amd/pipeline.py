@@ -163,6 +163,14 @@ class ForwardPipeline:
         s.done.synchronize()
         return s.boxes, s.scores, s.labels, s.counts
 
+    def outputs(self, ticket: int):
+        """The same four tensors of forward `ticket` WITHOUT waiting for it: for work enqueued on the device behind `wait(ticket)` (scoring the
+        batch where it lies, `voceval.VocAccumulator.update`). They are the slot's own buffers, overwritten by submit number ticket + depth;
+        that is safe for whatever was enqueued on the caller's stream before that submit, because submit makes the slot's stream wait for the
+        caller's stream before the forward starts."""
+        s = self._slot_of(ticket)
+        return s.boxes, s.scores, s.labels, s.counts
+
     def detections(self, ticket: int):
         """The reference's output form for forward `ticket`: List[Dict[boxes, scores, labels]] (generalized_ssd.py:392-396)."""
         boxes, scores, labels, counts = self.result(ticket)

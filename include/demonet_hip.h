@@ -314,6 +314,37 @@ DN_API int dn_merge_detections(const float* boxes_dev, const float* scores_dev, 
                                int class_agnostic, int d_out, float* boxes_out_dev, float* scores_out_dev, int64_t* labels_out_dev,
                                int32_t* counts_out_dev, int32_t* src_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* PASCAL VOC true / false positive marking on the device (csrc/evalmatch.hip): the per-image part of the reference's voc_eval
+ * (data/voc_eval.py:116-155) on the arrays dn_forward wrote, for several overlap thresholds in one launch. demonet_amd/voceval.py accumulates the
+ * flags and finishes precision / recall / AP; engine.evaluate_voc is the loop around it.
+ * Inputs: boxes [n][d][4] fp32 xyxy, scores [n][d] fp32, labels [n][d] int64, counts [n] int32 (dn_forward's outputs); gt_boxes [n][gmax][4] fp32,
+ * gt_labels [n][gmax] int64, gt_difficult [n][gmax] uint8 (may be NULL: none difficult), gt_counts [n] int32, padded as dn_ssd_loss takes them.
+ * thresholds is a HOST array [n_thresh], read during the call only. Per image i, with c = counts[i] and g = gt_counts[i] (each clamped to its
+ * array), all arithmetic in double on the fp32 inputs converted to double, one rounding per operation, in exactly this order (= numpy's float64):
+ *   1. candidates: the rows j < c; the row order is not assumed;
+ *   2. best ground truth of a candidate (x1, y1, x2, y2) with label L, over the ground truths k < g with gt_labels[k] == L, o = pixel_offset:
+ *        iw = max(min(gx2, x2) - max(gx1, x1) + o, 0), ih likewise (min / max as numpy's: a NaN operand gives NaN), inter = iw * ih,
+ *        union = (x2 - x1 + o) * (y2 - y1 + o) + (gx2 - gx1 + o) * (gy2 - gy1 + o) - inter, ov = inter / union;
+ *      best_ov = the maximum, best_gt = the lowest k that attains it (numpy's argmax); no ground truth of that label: best_ov = -inf, best_gt = -1;
+ *      any of these ov NaN: best_ov = NaN, best_gt = -1 and the candidate is a false positive at every threshold (NaN > t is false).
+ *      Ground-truth boxes must be finite: the caller's contract;
+ *   3. rank inside the image: score descending, NaN scores last, ties by ascending slot j;
+ *   4. for each threshold t (index b), in rank order with a fresh "claimed" bit per ground truth: best_ov > t (strict, double against double) and
+ *      the ground truth difficult: neither flag; best_ov > t, not difficult, unclaimed: TP (bit b) and the ground truth is claimed; best_ov > t,
+ *      not difficult, claimed: FP (bit 16 + b); best_ov > t false: FP. Rows j >= c: flags 0, best_gt -1, best_ov 0;
+ *   5. for every k < g with 0 <= gt_labels[k] < num_classes: gt_stats[label][difficult ? 1 : 0] += 1 (integer atomics; other labels are not counted).
+ * Outputs: flags [n][d] uint32, best_gt [n][d] int32 (may be NULL), best_ov [n][d] double (may be NULL), gt_stats [num_classes][2] int64 (may be
+ * NULL; ADDED to: the caller zeroes it). One launch, one workgroup per image, no workspace.
+ * Limits: d 1 .. 512, gmax 1 .. 1 024, n_thresh 1 .. 16, n 1 .. 65 535: DN_E_UNSUPPORTED beyond them. DN_E_INVALID for null required pointers,
+ * non-positive sizes, num_classes < 1 with gt_stats given, a NaN threshold, a pixel_offset that is not finite or negative, boxes / gt_boxes not
+ * 16-byte aligned, labels / gt_labels / best_ov / gt_stats not 8-byte aligned. Every argument is checked before the launch. Asynchronous on
+ * `stream`, no host synchronisation, can be captured; deterministic. */
+DN_API int dn_match_detections(const float* boxes_dev, const float* scores_dev, const int64_t* labels_dev, const int32_t* counts_dev,
+                               const float* gt_boxes_dev, const int64_t* gt_labels_dev, const uint8_t* gt_difficult_dev,
+                               const int32_t* gt_counts_dev, int n, int d, int gmax, int num_classes, const double* thresholds, int n_thresh,
+                               double pixel_offset, uint32_t* flags_dev, int32_t* best_gt_dev, double* best_ov_dev, int64_t* gt_stats_dev,
+                               void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
