@@ -7,7 +7,8 @@ while the host converts the previous ones: same `{image_id: {"boxes", "scores", 
 The COCO evaluator itself (pycocotools, `data/coco_eval.py`) is third-party and absent here; `evalrec.coco_detection_records`
 turns the records into the list `CocoEvaluator.prepare_for_coco_detection` builds (data/coco_eval.py:76-98) and
 `evalrec.voc_mean_ap` scores them the PASCAL VOC way. `evaluate_voc` is the same loop with the scoring on the device: the detections stay
-there and only the mAP comes back (demonet_amd/voceval.py).
+there and only the mAP comes back (demonet_amd/voceval.py). `evaluate_coco` is that loop with pycocotools' matching and its twelve numbers
+(demonet_amd/cocoeval.py).
 """
 import collections
 import time
@@ -84,20 +85,12 @@ def evaluate(model, data_loader: Iterable, device="cuda:0", depth: int = 3) -> T
     return results, {"images": n_images, "seconds": dt, "images_per_sec": n_images / max(dt, 1e-9), "model_seconds": model_time}
 
 
-@torch.no_grad()
-def evaluate_voc(model, data_loader: Iterable, device="cuda:0", depth: int = 3, thresholds=(0.5,), use_07_metric: bool = False,
-                 pixel_offset: float = 1.0) -> Tuple[dict, Dict[str, float]]:
-    """PASCAL VOC mAP of `model` over `data_loader` with the detections left on the device (DESIGN 4j). The loop is `evaluate`'s; the targets
-    hold the reference's `boxes` [k, 4] xyxy, `labels` [k] and, optionally, `difficult` [k] (num_classes is the model's). A batch's detections
-    never reach the host: once its slot is about to be reused, the current stream waits for the forward (`pipe.wait`) and
-    `voceval.VocAccumulator.update` marks true and false positives there, on the slot's own output tensors (`pipe.outputs`), and keeps copies
-    of scores, labels and flags on the device; the next submit on that slot orders itself behind the current stream. A batch of mixed sizes
-    is run by `model(images)` after the pipeline has drained and padded to [n][detections_per_img]. Only `summarize` waits for the device.
-    Returns (VocAccumulator.summarize(use_07_metric), stats) with the stats keys of `evaluate`; "seconds" includes the summary."""
-    from .voceval import VocAccumulator
-    device = torch.device(device)
+def _evaluate_on_device(model, data_loader: Iterable, device, depth: int, acc) -> Tuple[int, float]:
+    """`evaluate`'s loop with the detections left on the device: every batch goes to `acc.update(boxes, scores, labels, counts, targets)` on the
+    current stream once its slot is about to be reused (`pipe.wait`: the current stream waits, the host does not), on the slot's own output
+    tensors (`pipe.outputs`); the next submit on that slot orders itself behind the current stream. A batch of mixed sizes is run by
+    `model(images)` after the pipeline has drained and padded to [n][detections_per_img]. Returns (images, model_seconds)."""
     model.eval()
-    acc = VocAccumulator(model.graph.num_classes, thresholds, pixel_offset)
     pending = collections.deque()
     pipe = None
     shape = None
@@ -112,7 +105,6 @@ def evaluate_voc(model, data_loader: Iterable, device="cuda:0", depth: int = 3, 
         while pending:
             collect(*pending.popleft())
 
-    t_start = time.perf_counter()
     for images, targets in data_loader:
         same = isinstance(images, torch.Tensor) or len({tuple(im.shape) for im in images}) == 1
         t0 = time.perf_counter()
@@ -146,9 +138,50 @@ def evaluate_voc(model, data_loader: Iterable, device="cuda:0", depth: int = 3, 
     if pipe is not None:
         pipe.close()
     model_time += time.perf_counter() - t0
+    return n_images, model_time
+
+
+@torch.no_grad()
+def evaluate_voc(model, data_loader: Iterable, device="cuda:0", depth: int = 3, thresholds=(0.5,), use_07_metric: bool = False,
+                 pixel_offset: float = 1.0) -> Tuple[dict, Dict[str, float]]:
+    """PASCAL VOC mAP of `model` over `data_loader` with the detections left on the device (DESIGN 4j). The loop is `evaluate`'s; the targets
+    hold the reference's `boxes` [k, 4] xyxy, `labels` [k] and, optionally, `difficult` [k] (num_classes is the model's). A batch's detections
+    never reach the host: once its slot is about to be reused, the current stream waits for the forward (`pipe.wait`) and
+    `voceval.VocAccumulator.update` marks true and false positives there, on the slot's own output tensors (`pipe.outputs`), and keeps copies
+    of scores, labels and flags on the device; the next submit on that slot orders itself behind the current stream. A batch of mixed sizes
+    is run by `model(images)` after the pipeline has drained and padded to [n][detections_per_img]. Only `summarize` waits for the device.
+    Returns (VocAccumulator.summarize(use_07_metric), stats) with the stats keys of `evaluate`; "seconds" includes the summary."""
+    from .voceval import VocAccumulator
+    device = torch.device(device)
+    acc = VocAccumulator(model.graph.num_classes, thresholds, pixel_offset)
+    t_start = time.perf_counter()
+    n_images, model_time = _evaluate_on_device(model, data_loader, device, depth, acc)
     summary = acc.summarize(use_07_metric)
     dt = time.perf_counter() - t_start
     return summary, {"images": n_images, "seconds": dt, "images_per_sec": n_images / max(dt, 1e-9), "model_seconds": model_time}
+
+
+@torch.no_grad()
+def evaluate_coco(model, data_loader: Iterable, device="cuda:0", depth: int = 3, iou_thresholds=None, area_ranges=None,
+                  max_dets=(1, 10, 100)) -> Tuple[dict, Dict[str, float]]:
+    """The COCO numbers of `model` over `data_loader` with the detections left on the device: what the reference's `evaluate` gets
+    from `CocoEvaluator` (data/coco_eval.py:23-64) and pycocotools. The loop is `evaluate_voc`'s; the targets hold the reference's `boxes`
+    [k, 4] xyxy, `labels` [k] and, optionally, `iscrowd` [k] and `area` [k] (num_classes is the model's; the loader's order stands in for
+    ascending image ids). `cocoeval.CocoAccumulator.update` matches every batch on the device and keeps scores, labels, flags and ranks
+    there; only `summarize` waits for the device. Returns (CocoAccumulator.summarize() = {"stats": the twelve numbers, "precision", "recall"},
+    stats) with the stats keys of `evaluate`; "seconds" includes the summary, "summarize_seconds" is the summary alone."""
+    from . import cocoeval
+    device = torch.device(device)
+    acc = cocoeval.CocoAccumulator(model.graph.num_classes, cocoeval.IOU_THRESHOLDS if iou_thresholds is None else iou_thresholds,
+                                   cocoeval.AREA_RANGES if area_ranges is None else area_ranges, max_dets)
+    t_start = time.perf_counter()
+    n_images, model_time = _evaluate_on_device(model, data_loader, device, depth, acc)
+    t0 = time.perf_counter()
+    summary = acc.summarize()
+    t1 = time.perf_counter()
+    dt = t1 - t_start
+    return summary, {"images": n_images, "seconds": dt, "images_per_sec": n_images / max(dt, 1e-9), "model_seconds": model_time,
+                     "summarize_seconds": t1 - t0}
 
 
 def coco_records(results: Dict[int, Dict[str, torch.Tensor]]) -> List[dict]:

@@ -345,6 +345,39 @@ DN_API int dn_match_detections(const float* boxes_dev, const float* scores_dev, 
                                double pixel_offset, uint32_t* flags_dev, int32_t* best_gt_dev, double* best_ov_dev, int64_t* gt_stats_dev,
                                void* stream);
 
+/* COCO detection matching on the device (csrc/cocomatch.hip): the per-image part of pycocotools' COCOeval (computeIoU + evaluateImg for
+ * bounding boxes, useCats = 1) on the arrays dn_forward wrote, for several IoU thresholds and area ranges in one launch. demonet_amd/cocoeval.py
+ * accumulates the flags and finishes precision / recall / the twelve COCO numbers (accumulate + summarize); engine.evaluate_coco is the loop.
+ * Inputs: boxes [n][d][4] fp32 xyxy, scores [n][d] fp32, labels [n][d] int64, counts [n] int32 (dn_forward's outputs); gt_boxes [n][gmax][4] fp32
+ * xyxy, gt_labels [n][gmax] int64, gt_counts [n] int32, gt_crowd [n][gmax] uint8 (may be NULL: none; nonzero = the annotation's iscrowd or ignore),
+ * gt_area [n][gmax] fp32 (may be NULL: w * h of the box; COCO's area is the segmentation's). thresholds [n_thresh] and area_ranges [n_ranges][2]
+ * (lo, hi) are HOST arrays, read during the call only. Per image i, with c = counts[i] and g = gt_counts[i] (each clamped to its array); a
+ * category = the rows of one label; all arithmetic in double, one rounding per operation, in exactly this order:
+ *   1. boxes become (x, y, w, h) with w = fp32(x2 - x1), h = fp32(y2 - y1), detections and ground truths alike, then double;
+ *   2. rank of a detection inside (image, category): score descending, NaN scores last, ties by ascending slot. Only ranks < max_det take part;
+ *   3. IoU of detection (dx, dy, dw, dh) and ground truth (gx, gy, gw, gh): iw = fmin(dw + dx, gw + gx) - fmax(dx, gx); iw <= 0: IoU = 0;
+ *      ih likewise on y; i = iw * ih; u = crowd ? dw * dh : dw * dh + gw * gh - i; IoU = i / u. No pixel offset;
+ *   4. for range r = (lo, hi) a ground truth is ignored if it is crowd or area < lo or area > hi (both ends inclusive), area = gt_area or
+ *      double(gw) * double(gh);
+ *   5. the walk, for each threshold t (index b) and range r, over the category's detections in rank order: bar = min(t, 1 - 1e-10), match = none;
+ *      pass 1 over the category's not-ignored ground truths in slot order, pass 2 over its ignored ones in slot order, pass 2 skipped when pass 1
+ *      found a match; a ground truth already matched at (t, r) is skipped unless it is crowd; one with IoU < bar is skipped; any other becomes
+ *      the match and bar = its IoU (a later equal IoU replaces it). A match marks the ground truth matched at (t, r), sets bit b of the
+ *      detection's flags word for r and, if the ground truth is ignored in r, bit 16 + b. No match: bit 16 + b if dw * dh < lo or dw * dh > hi;
+ *   6. for every k < g with 0 <= gt_labels[k] < num_classes and every r in which k is not ignored: gt_stats[label][r] += 1 (integer atomics).
+ * Outputs: flags [n][d][n_ranges] uint32 (0 for rows >= c and for ranks >= max_det), rank [n][d] int32 (-1 for rows >= c; not cut at max_det),
+ * match_gt [n][d][n_ranges][n_thresh] int32 (may be NULL) = the matched ground truth's slot or -1, gt_stats [num_classes][n_ranges] int64 (may be
+ * NULL; ADDED to: the caller zeroes it). Every element of every output given is written. One launch, one workgroup per image, no workspace.
+ * Limits: d 1 .. 512, gmax 1 .. 1 024, n_thresh 1 .. 16, n_ranges 1 .. 4, max_det 1 .. 128, n 1 .. 65 535: DN_E_UNSUPPORTED above them.
+ * DN_E_INVALID for null required pointers, non-positive sizes or max_det, num_classes < 1 with gt_stats given, a NaN threshold or range end,
+ * boxes / gt_boxes not 16-byte aligned, labels / gt_labels / gt_stats not 8-byte aligned, the other arrays not 4-byte aligned. Every argument is
+ * checked before the launch. Asynchronous on `stream`, no host synchronisation, can be captured; deterministic. */
+DN_API int dn_coco_match(const float* boxes_dev, const float* scores_dev, const int64_t* labels_dev, const int32_t* counts_dev,
+                         const float* gt_boxes_dev, const int64_t* gt_labels_dev, const int32_t* gt_counts_dev, const uint8_t* gt_crowd_dev,
+                         const float* gt_area_dev, int n, int d, int gmax, int num_classes, const double* thresholds, int n_thresh,
+                         const double* area_ranges, int n_ranges, int max_det, uint32_t* flags_dev, int32_t* rank_dev, int32_t* match_gt_dev,
+                         int64_t* gt_stats_dev, void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
