@@ -1442,6 +1442,16 @@ extern "C" int dn_tensor_ptr(const dn_plan* p, void* workspace, int n, int tenso
     return DN_OK;
 }
 
+// test support (include/demonet_hip_debug.h): what the stem of an n-image forward reads after a resize or a uint8 conversion -- the
+// [n][3][image_h][image_w] fp32 block and the [n][2] (w, h) ratios, both contiguous over the sub-batch chains (get_sub_layout)
+extern "C" __attribute__((visibility("default"))) int dn_debug_network_input(const dn_plan* p, void* workspace, int n, float** resized, float** scale_xy) {
+    DN_REQUIRE(p && workspace && n > 0, "dn_debug_network_input: bad argument");
+    const Layout& L = get_layout(const_cast<dn_plan*>(p), n);
+    if (resized) *resized = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + L.resized_off);
+    if (scale_xy) *scale_xy = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + L.scale_off);
+    return DN_OK;
+}
+
 extern "C" int dn_batch_split(const dn_plan* p, int n) {
     DN_REQUIRE(p && n > 0, "dn_batch_split: bad argument");
     return batch_split(p, n);

@@ -31,6 +31,16 @@ CONFIGS = ([(V3, 91, n, {}, None) for n in (2, 16, 37, 64)]
               ("ssd300_vgg16", 91, 5, {}, None), ("ssd300_vgg16", 91, 9, {}, None), ("ssd512_vgg16", 91, 3, {}, None),
               # the signature records conv_halo_kernel<3,8,2,head> (ssd300) and pw_kernel<64,64,2,2,true,32> (ssd512) at n = 16 only
               ("ssd300_vgg16", 91, 16, {}, None), ("ssd512_vgg16", 91, 16, {}, None)])
+# The V2 plan at other network sizes: every decision of the planner and the choice functions that depends on a map size takes one branch
+# at 300 / 320. 160: level 1 is 5 x 5 (under the 32 pixels of the softmax epilogue), the 160- / 320-channel blocks and the 1280-channel 1x1
+# become tail-eligible; 192: level 1 is 6 x 6; 224: 7 -> 4 -> 2 -> 1 -> 1; 301: an odd input, a stem column without a right neighbour;
+# 496 / 512: level 0 is 31 / 32 wide, the last width the fused head launch takes and the first it does not; 640: 40 x 40, the last level
+# 2 x 2. 9 images: XCD grouping with ragged groups.
+V2_SIZES = (160, 192, 224, 256, 301, 384, 496, 512, 640)
+SIZE_CONFIGS = ([(V2, 21, 2 if size == 640 else 3, {}, size) for size in V2_SIZES]
+                + [(V2, 21, 9, {}, size) for size in (160, 301, 496)]
+                + [(V2, 21, 3, {k: "0"}, size) for size in (160, 512) for k in ("DN_TAIL", "DN_HEAD_FUSE")])
+CONFIGS = CONFIGS + SIZE_CONFIGS
 
 
 def _cid(c):
@@ -59,7 +69,8 @@ def _model(name, ncls, size, dev):
 
 
 def _labels(m, imgs, dev):
-    """per op: the label of the launch it took part in (dn_profile_op_info after one profiled forward_batch)"""
+    """per op: the label of the launch it took part in and the op that owns that launch's time segment (dn_profile_op_info after one
+    profiled forward_batch)"""
     L = _lib.lib()
     h = C.c_void_p(m._plan(dev))
     _lib.check(L.dn_profile_begin(h))
@@ -67,13 +78,14 @@ def _labels(m, imgs, dev):
     nseg = len(m.graph.nodes) + 4
     _lib.check(L.dn_profile_end(h, (C.c_float * nseg)(), nseg))
     label, owner = C.create_string_buffer(96), C.c_int32()
-    out = []
+    out, owners = [], []
     for i in range(len(m.graph.nodes)):
         _lib.check(L.dn_profile_op_info(h, i, label, 96, C.byref(owner)))
         # forward_heads never runs the softmax epilogue of the fused head launch (dn_forward does, from 32 images per chain): the
         # instantiation checked here is the plain one
         out.append(label.value.decode().replace(",softmax", ""))
-    return out
+        owners.append(int(owner.value))
+    return out, owners
 
 
 class _Stats:
@@ -117,7 +129,7 @@ def _run(cfg):
         W, H = g.size
         imgs = torch.from_numpy(synth.images(11, n, H, W))
         imgs_d = imgs.to(dev)
-        labels = _labels(lab_m, imgs_d, dev)
+        labels, owners = _labels(lab_m, imgs_d, dev)
         ref_logits, ref_reg = lab_m.forward_heads(imgs_d)            # the default plan (workspace reuse as configured by default)
         torch.cuda.synchronize()
         lab_m.release()
@@ -171,7 +183,7 @@ def _run(cfg):
             fails.append(f"head array {what}: {u} of {arr.numel()} elements not written")
     if fails:
         m.release()
-        return _CACHE.setdefault(key, dict(labels=labels, stats=stats, fails=fails, seconds=time.time() - t0))
+        return _CACHE.setdefault(key, dict(labels=labels, owners=owners, graph=g, stats=stats, fails=fails, seconds=time.time() - t0))
     # carry-over to the default plan
     if not (torch.equal(logits, ref_logits) and torch.equal(reg, ref_reg)):
         fails.append(f"head outputs of the DN_WS_REUSE=0 plan differ from the default plan's: "
@@ -233,7 +245,7 @@ def _run(cfg):
                     val.pop(tid, None)
                     err.pop(tid, None)
     m.release()
-    return _CACHE.setdefault(key, dict(labels=labels, stats=stats, fails=fails, seconds=time.time() - t0))
+    return _CACHE.setdefault(key, dict(labels=labels, owners=owners, graph=g, stats=stats, fails=fails, seconds=time.time() - t0))
 
 
 def _report(res, title):
@@ -249,6 +261,73 @@ def test_launch_parity(cfg):
     res = _run(cfg)
     print("\n" + _report(res, _cid(cfg)))
     assert not res["fails"], "\n".join(res["fails"][:20])
+
+
+def _tail_op_supported(g, nd):
+    """tail.hip tail_op_supported on a graph node (the fragment-major weight copy every 1x1 of these graphs has is taken for granted)"""
+    ti, to = g.t(nd.inp), g.t(nd.out)
+    if nd.head or nd.residual >= 0 or nd.se >= 0 or nd.pool >= 0:
+        return False
+    if nd.op == "pw":
+        return to.h * to.w <= 32 and nd.cin % 16 == 0 and nd.cout % 8 == 0 and nd.cin <= 2048 and nd.cout <= 2048
+    if nd.op == "dw":
+        return to.h * to.w <= 32 and ti.h * ti.w <= 128 and nd.cin % 8 == 0 and nd.dil == 1 and nd.k in (3, 5)
+    return False
+
+
+@pytest.mark.parametrize("cfg", SIZE_CONFIGS, ids=[_cid(c) for c in SIZE_CONFIGS])
+def test_the_launches_are_the_ones_the_map_sizes_call_for(cfg):
+    """Which path ran, from the graph's map sizes alone: a plan that quietly left everything on the per-op and grouped launches would pass the
+    parity test. Fused head launch: the levels whose heads are depthwise -> 1x1 on a map of W <= 31 with C % 32 == 0 and ReLU6
+    (headfuse.hip head_fused_level_supported; the V2 model's last level is a plain 1x1). Tail run: the longest linear suffix of the backbone
+    whose ops pass tail_op_supported and are not part of an earlier multi-op launch, cut to TAIL_MAX_OPS = 16, at least two ops."""
+    name, ncls, n, env, size = cfg
+    res = _run(cfg)
+    g, labels, owners = res["graph"], res["labels"], res["owners"]
+    nodes = g.nodes
+    producer = {nd.out: i for i, nd in enumerate(nodes)}
+    # ---- the fused head launch
+    want_levels = set()
+    for i, nd in enumerate(nodes):
+        if nd.head != 1 or nd.op != "pw":
+            continue
+        d = nodes[producer[nd.inp]] if nd.inp not in g.features else None
+        t = g.t(g.features[nd.level])
+        if d is not None and d.op == "dw" and t.w <= 31 and t.c % 32 == 0 and t.c >= 32 and d.act == 2 and env.get("DN_HEAD_FUSE", "1") != "0":
+            want_levels.add(nd.level)
+    got_levels = set()
+    for i, nd in enumerate(nodes):
+        if nd.head and nd.op == "pw":
+            ops = [i] + ([producer[nd.inp]] if nd.inp not in g.features else [])
+            fused = [labels[q].startswith("head_fused_kernel") for q in ops]
+            assert all(fused) or not any(fused), f"level {nd.level}: {[labels[q] for q in ops]}"
+            if fused[0]:
+                got_levels.add(nd.level)
+            else:
+                assert nd.level not in want_levels, f"level {nd.level} ({g.t(g.features[nd.level]).w} wide) left the fused head launch: {labels[i]}"
+    assert got_levels == want_levels, (sorted(got_levels), sorted(want_levels))
+    widths = [g.t(f).w for f in g.features]
+    assert want_levels == (set() if env.get("DN_HEAD_FUSE") == "0" else {l for l in range(5) if widths[l] <= 31}), (widths, want_levels)
+    # ---- the tail run
+    end = min(i for i, nd in enumerate(nodes) if nd.head or any(u.head and u.inp == nd.out and nd.out not in g.features for u in nodes))
+    members = {}
+    for i, o in enumerate(owners):
+        members.setdefault(o, []).append(i)
+    other_launch = lambda i: labels[i] != "tail_kernel" and len(members[owners[i]]) > 1       # grouped before the tail pass (expand -> depthwise -> project)
+    first = end
+    while first > 0:
+        i = first - 1
+        if other_launch(i) or not _tail_op_supported(g, nodes[i]) or (first < end and nodes[first].inp != nodes[i].out):
+            break
+        first -= 1
+    first = max(first, end - 16)
+    want_tail = set(range(first, end)) if end - first >= 2 and env.get("DN_TAIL", "1") != "0" else set()
+    got_tail = {i for i, lab in enumerate(labels) if lab == "tail_kernel"}
+    print(f"\n{_cid(cfg)}: fused head levels {sorted(got_levels)} of widths {widths}; tail run ops {min(got_tail, default=-1)} .. {max(got_tail, default=-1)} "
+          f"({len(got_tail)} ops), backbone ends at {end}")
+    assert got_tail == want_tail, (sorted(got_tail), sorted(want_tail))
+    if env.get("DN_TAIL", "1") != "0":
+        assert len(want_tail) >= 8, "every size has the extra layers' tiny maps in its tail run"
 
 
 def test_parity_covers_every_signature_label(golden_dir):

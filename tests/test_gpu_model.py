@@ -1094,7 +1094,8 @@ def test_vgg_without_workspace_reuse(name, n, size, monkeypatch):
                                                ("ssdlite320_mobilenet_v3_large", 21, 9, {}),
                                                ("ssdlite320_mobilenet_v3_large", 91, 5, {"score_thresh": 0.05, "detections_per_img": 100, "topk_candidates": 200}),
                                                ("ssdlite320_mobilenet_v3_large", 91, 8, {"score_thresh": 1e-6}),
-                                               ("ssd_lite_mobilenet_v2", 21, 40, {"image_size": 300}), ("ssd_lite_mobilenet_v2", 91, 5, {})])
+                                               ("ssd_lite_mobilenet_v2", 21, 40, {"image_size": 300}), ("ssd_lite_mobilenet_v2", 91, 5, {})]
+                         + [("ssd_lite_mobilenet_v2", 21, 5, {"image_size": s}) for s in (160, 192, 301, 496, 512)])
 def test_softmax_and_decode_in_the_head_launch_are_bit_identical(name, ncls, n, post, monkeypatch):
     """Round 5 (headfuse.hip SM = true, DN_HEAD_SOFTMAX default 1): softmax over the classes, decode_single + clip and the score-histogram rows
     (generalized_ssd.py:354,362-363; _utils.py:187-224) run in the epilogue of the fused head launch -- the logits never reach memory and
@@ -1105,11 +1106,14 @@ def test_softmax_and_decode_in_the_head_launch_are_bit_identical(name, ncls, n, 
     softmax from a few tiles of softmax_decode_kernel (one score array, one histogram-row table for both). Batch 64 (XCD grouping: 8 images per
     group, tiles spanning two images), 37 (two chains, ragged groups), 3 and 1 (plain mapping), K = 21 (126 channels per pixel: other row
     geometry), non-default thresholds (a clamped / shifted histogram range), the V2 model at 300 x 300 (19 x 19 / 10 x 10 maps; its last level
-    is a plain 1x1 conv outside the fused launch) and at 320."""
+    is a plain 1x1 conv outside the fused launch) and at 320. The V2 model at other network sizes: 160 (only level 0 has 32 pixels), 192
+    (level 1 is 6 x 6), 301, 496 (level 0 is 31 wide) and 512, where the 32-wide level 0 is outside the fused launch, the epilogue levels
+    are no prefix of the pyramid and the epilogue must not launch (head_fused_post_supported, plan.hip head_softmax_epilogue)."""
     import ctypes
     from demonet_amd import _lib
     raw = ctypes.CDLL(_lib.LIB_PATH)
     size = post.get("image_size", 320)
+    epilogue = size != 512
     imgs = torch.from_numpy(synth.images(83, n, size, size)).cuda()
     res, launches = {}, {}
     monkeypatch.setenv("DN_HEAD_SOFTMAX_MINN", "1")          # (by default the epilogue is used from 32 images per chain up)
@@ -1122,10 +1126,29 @@ def test_softmax_and_decode_in_the_head_launch_are_bit_identical(name, ncls, n, 
         again = m.forward_batch(imgs)                       # graph replay
         for x, y in zip(res[flag], again):
             assert torch.equal(x, y)
-    assert launches["0"] == 0 and launches["1"] >= 1, launches
+    assert launches["0"] == 0 and (launches["1"] >= 1 if epilogue else launches["1"] == 0), launches
     assert int(res["1"][3].min()) > 0
     for q, what in enumerate(("boxes", "scores", "labels", "counts")):
         assert torch.equal(res["0"][q], res["1"][q]), what
+
+
+@pytest.mark.parametrize("size", [160, 192, 224, 256, 301, 384, 496, 512, 640])
+def test_graph_replay_equals_the_first_forward_at_other_network_sizes(size):
+    """the V2 model at the network sizes of tests/test_gpu_launch_parity.py: the second forward_batch -- the replay of the captured graph --
+    equals the first bit for bit, detections and head outputs"""
+    n = 2 if size == 640 else 3
+    m = _model("ssd_lite_mobilenet_v2", num_classes=21, image_size=size)
+    imgs = torch.from_numpy(synth.images(97, n, size, size)).cuda()
+    first = [t.clone() for t in m.forward_batch(imgs, persistent_input=True)]
+    for _ in range(2):
+        again = m.forward_batch(imgs, persistent_input=True)
+        for x, y, what in zip(first, again, ("boxes", "scores", "labels", "counts")):
+            assert torch.equal(x, y), what
+    assert int(first[3].sum()) > 0
+    heads = [t.clone() for t in m.forward_heads(imgs)]
+    for x, y in zip(heads, m.forward_heads(imgs)):
+        assert torch.equal(x, y) and bool(torch.isfinite(x).all())
+    m.release()
 
 
 def test_softmax_in_the_head_launch_feeds_the_same_cut_off(monkeypatch):

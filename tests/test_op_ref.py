@@ -44,16 +44,26 @@ def test_fp32_chain_matches_golden(golden_dir, name):
         np.testing.assert_allclose(samp, z[f"feat{lvl}_sample"], rtol=1e-4, atol=2e-4)
 
 
-def test_fp32_chain_matches_oracle_v2_at_300():
-    """BASELINE config C3: the V2 hub model at 300 x 300 (ragged maps down the pyramid) against the oracle"""
-    g = spec.ssd_lite_mobilenet_v2_graph(image_size=300, num_classes=21)
+def _v2_chain_against_the_oracle(size):
+    g = spec.ssd_lite_mobilenet_v2_graph(image_size=size, num_classes=21)
     sd = synth.state_dict(g, 0)
-    imgs = torch.from_numpy(synth.images(3, 2, 300, 300))
+    imgs = torch.from_numpy(synth.images(3, 2, size, size))
     with torch.no_grad():
         lg, rg, _ = op_ref.chain(g, sd, imgs)
-    raw = so.OracleSSD("ssd_lite_mobilenet_v2", sd, 21, size=(300, 300)).forward_raw(list(imgs))
+    raw = so.OracleSSD("ssd_lite_mobilenet_v2", sd, 21, size=(size, size)).forward_raw(list(imgs))
     np.testing.assert_allclose(lg.numpy(), raw["cls_logits"].numpy(), rtol=1e-4, atol=2e-4)
     np.testing.assert_allclose(rg.numpy(), raw["bbox_regression"].numpy(), rtol=1e-4, atol=2e-4)
+
+
+def test_fp32_chain_matches_oracle_v2_at_300():
+    """BASELINE config C3: the V2 hub model at 300 x 300 (ragged maps down the pyramid) against the oracle"""
+    _v2_chain_against_the_oracle(300)
+
+
+@pytest.mark.parametrize("size", [160, 301])
+def test_fp32_chain_matches_oracle_v2_at_other_sizes(size):
+    """160: a 5 x 5 second level, the smallest network tests/test_gpu_launch_parity.py runs; 301: an odd input, 151 -> 76 -> 38 -> 19"""
+    _v2_chain_against_the_oracle(size)
 
 
 # ---- sensitivity: emulated kernels through the same comparator -----------------------------------------------------------------------

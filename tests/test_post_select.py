@@ -764,17 +764,24 @@ def _hard_op_on_heads(m, imgs):
     return boxes, scores, labels, counts
 
 
+# the V2 model at other network sizes, the epilogue allowed from one image per chain: it engages where the levels of >= 32 pixels are the
+# pyramid levels 0 .. k of the fused head launch (at 160 level 0 alone: level 1 is 5 x 5) and not at 512, whose 32-wide level 0 is outside it
+_V2_SIZES = [(160, True), (192, True), (301, True), (496, True), (512, False)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("name,kw,n,epilogue", [("ssdlite320_mobilenet_v3_large", {}, 3, False), ("ssdlite320_mobilenet_v3_large", {}, 37, True),
-                                                 ("ssd_lite_mobilenet_v2", dict(image_size=300, score_thresh=0.01), 3, False), ("ssd300_vgg16", {}, 3, False)],
-                         ids=["v3-n3", "v3-n37-epilogue", "v2-300-n3", "vgg300-n3"])
-def test_model_forward_in_hard_mode_is_the_op_on_its_head_outputs(name, kw, n, epilogue, monkeypatch):
+@pytest.mark.parametrize("name,kw,n,minn,epilogue",
+                         [("ssdlite320_mobilenet_v3_large", {}, 3, None, False), ("ssdlite320_mobilenet_v3_large", {}, 37, 16, True),
+                          ("ssd_lite_mobilenet_v2", dict(image_size=300, score_thresh=0.01), 3, None, False), ("ssd300_vgg16", {}, 3, None, False)]
+                         + [("ssd_lite_mobilenet_v2", dict(image_size=s, score_thresh=0.01), 3, 1, e) for s, e in _V2_SIZES],
+                         ids=["v3-n3", "v3-n37-epilogue", "v2-300-n3", "vgg300-n3"] + [f"v2-{s}-n3-minn1" for s, _ in _V2_SIZES])
+def test_model_forward_in_hard_mode_is_the_op_on_its_head_outputs(name, kw, n, minn, epilogue, monkeypatch):
     """model.forward_batch == dn_postprocess(forward_heads) bit for bit (labels, scores, boxes, counts): the forward's post-process reads scores
     stored through the plan's level table, and with the fused head epilogue (37 images: chains of 19 and 18 at a threshold of 16) scores the
     head launch computed -- neither can be reached through dn_postprocess, whose exactness the rest of this module holds."""
     raw = C.CDLL(_lib.LIB_PATH)
-    if epilogue:
-        monkeypatch.setenv("DN_HEAD_SOFTMAX_MINN", "16")
+    if minn is not None:
+        monkeypatch.setenv("DN_HEAD_SOFTMAX_MINN", str(minn))
     m = _model(name, 21, **kw)
     assert m.nms_method == "hard"
     W, H = m.graph.size
