@@ -478,6 +478,15 @@ class SSD(_Tracked):
         logits, reg = self.forward_heads(images)
         return self.compute_loss(targets, {"cls_logits": logits, "bbox_regression": reg})
 
+    def train_preset(self, data_augmentation: str = "ssd", **kw):
+        """The reference's DetectionPresetTrain (presets.py:4-23) bound to this model's network size, on the device (demonet_amd/augment.py,
+        DESIGN 4l): preset(images, targets, generator=None) takes a list of decoded [h, w, 3] uint8 device tensors of any sizes with their
+        targets and returns (batch, targets) as SSD.loss takes them -- model.loss(*model.train_preset()(images, targets)) is the whole input
+        side of a fine-tuning step. kw: hflip_prob, mean and the other constructor arguments of augment.AugmentSampler."""
+        from .augment import DetectionPresetTrain
+        W, H = self.graph.size
+        return DetectionPresetTrain(data_augmentation, size=(H, W), **kw)
+
     def forward(self, images, targets: Optional[List[Dict[str, Tensor]]] = None):
         if self.training:
             if targets is None:

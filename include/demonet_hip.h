@@ -378,6 +378,41 @@ DN_API int dn_coco_match(const float* boxes_dev, const float* scores_dev, const 
                          const double* area_ranges, int n_ranges, int max_det, uint32_t* flags_dev, int32_t* rank_dev, int32_t* match_gt_dev,
                          int64_t* gt_stats_dev, void* stream);
 
+/* SSD training augmentation on the device (csrc/augment.hip): per batch, the reference's DetectionPresetTrain('ssd') (data/presets.py;
+ * data/transforms.py:190-239 RandomPhotometricDistort, :132-187 RandomZoomOut, :54-129 RandomIoUCrop, :30-44 RandomHorizontalFlip, :47-51 ToTensor) and
+ * the image half of the model transform's resize (transform.py:27-53, 150-173), from the decoder's output straight to the input of dn_forward /
+ * SSD.loss with no intermediate image. The random draws and the boxes (transforms.py:121-126, 184-185, 37; transform.py:278-292) are the caller's:
+ * demonet_amd/augment.py samples them; this call applies one parameter record per image.
+ * images: HOST array of n DEVICE pointers, image i = [h_i][w_i][3] uint8, HWC, RGB, contiguous; sizes: HOST int32 [n][2] = (h_i, w_i); params: HOST
+ * [n][DN_AUG_WORDS] 4-byte words (int32 or fp32 bits) as indexed below; out_dev [n][3][out_h][out_w] fp32 in [0, 1], NOT mean / std normalised (the
+ * plan's stem does that). Per image, with x = u8 / 255 in fp32, gray = 0.2989 r + 0.587 g + 0.114 b and blend(a, b, f) = clamp(f a + (1 - f) b, 0, 1)
+ * (torchvision's tensor formulas), each photometric step only when its flag is set, in this order:
+ *   brightness blend(x, 0, f) | contrast blend(x, mean of gray over the whole image as it stands at that point, f) if DN_AUG_F_CONTRAST_BEFORE |
+ *   saturation blend(x, gray(x), f) | hue: _rgb2hsv, h = (h + f) mod 1, _hsv2rgb | contrast otherwise | channels out[c] = in[perm[c]];
+ *   a canvas CANVAS_H x CANVAS_W with that image at (LEFT, TOP) and FILL[c] elsewhere (the fill is neither distorted nor permuted); the crop
+ *   (CROP_L, CROP_T, CROP_W, CROP_H) of the canvas; its horizontal flip if DN_AUG_F_FLIP; the bilinear resize (align_corners = False) of the crop
+ *   to out_h x out_w, the arithmetic of dn_forward's input resize.
+ * Launches: the contrast means (double sums of fixed chunks, fixed-shape tree, no float atomics; then one thread per image adds the partials in
+ * index order) and the output (gather, photometric chain per tap, blend); the output launch alone when no record has contrast on. Deterministic: the same bits on every run. DN_E_INVALID, with nothing launched, for a null pointer (an image's included), n, out_h,
+ * out_w or a size <= 0, unknown flag bits, an image placed outside its canvas (LEFT, TOP < 0 or LEFT + w > CANVAS_W or TOP + h > CANVAS_H), a crop
+ * that is empty or leaves the canvas, perm not a permutation of 0 1 2, a non-finite factor or fill, a workspace that is not 16-byte aligned or
+ * smaller than dn_augment_workspace_bytes(n) (0 for an n the call refuses); DN_E_UNSUPPORTED for n > 65 535, an image above 2^29 pixels or an output
+ * of 2^31. Whatever the record says, no byte outside an image's h_i x w_i x 3 is read. The three host arrays are read during the call only: the
+ * table goes into the workspace by ONE copy on `stream`, the launches are enqueued behind it, and THE CALL THEN WAITS FOR THAT COPY (the table is
+ * the call's own host memory; the launches go on behind it): like dn_crop_tiles an exception to this header's rule, and not capturable. */
+enum { DN_AUG_FLAGS = 0,                /* int32: DN_AUG_F_* bits */
+       DN_AUG_BRIGHTNESS = 1, DN_AUG_CONTRAST = 2, DN_AUG_SATURATION = 3, DN_AUG_HUE = 4,   /* fp32 factors (read only when the flag is set; always finite) */
+       DN_AUG_PERM = 5,                 /* int32 [3] */
+       DN_AUG_CANVAS_H = 8, DN_AUG_CANVAS_W = 9, DN_AUG_LEFT = 10, DN_AUG_TOP = 11,         /* int32 */
+       DN_AUG_FILL = 12,                /* fp32 [3], in [0, 1] units (the reference's default: (123, 117, 104) / 255) */
+       DN_AUG_CROP_L = 15, DN_AUG_CROP_T = 16, DN_AUG_CROP_W = 17, DN_AUG_CROP_H = 18,      /* int32, canvas coordinates */
+       DN_AUG_WORDS = 20 };             /* word 19: reserved, 0 */
+enum { DN_AUG_F_BRIGHTNESS = 1, DN_AUG_F_CONTRAST = 2, DN_AUG_F_SATURATION = 4, DN_AUG_F_HUE = 8, DN_AUG_F_CONTRAST_BEFORE = 16, DN_AUG_F_FLIP = 32,
+       DN_AUG_F_ALL = 63 };
+DN_API size_t dn_augment_workspace_bytes(int n);
+DN_API int dn_augment_batch(const uint8_t* const* images, const int32_t* sizes, const int32_t* params, int n, int out_h, int out_w,
+                            float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
