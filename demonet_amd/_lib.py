@@ -10,6 +10,8 @@ DN_OP = dict(stem=1, pw=2, dw=3, se=4, conv=5, maxpool=6, l2norm=7)
 DN_T = dict(act=0, image=1, vec=2, pool=3)
 DN_NMS = dict(hard=0, linear=1, gaussian=2)
 DN_MERGE = dict(iou=0, ios=1)
+DN_SGD_CHUNK = 2048
+DN_SGD_MAX_GATE = 8
 
 
 class TensorDesc(C.Structure):
@@ -24,6 +26,15 @@ class OpDesc(C.Structure):
                 ("head", C.c_int32), ("level", C.c_int32), ("squeeze", C.c_int32), ("ceil_mode", C.c_int32),
                 ("pool_pixels", C.c_int32), ("reserved", C.c_int32 * 2),
                 ("w_off", C.c_int64), ("b_off", C.c_int64), ("w2_off", C.c_int64), ("b2_off", C.c_int64)]
+
+
+class SgdTensor(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("buf", C.c_void_p), ("numel", C.c_int64)]
+
+
+class SgdHyper(C.Structure):
+    _fields_ = [("lr", C.c_float), ("momentum", C.c_float), ("dampening", C.c_float), ("weight_decay", C.c_float),
+                ("nesterov", C.c_int32), ("first_step", C.c_int32), ("step", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ModelDesc(C.Structure):
@@ -91,6 +102,9 @@ _SIGNATURES = {
     "dn_coco_match": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 4 + [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int] + [C.c_void_p] * 5),
     "dn_augment_workspace_bytes": (C.c_size_t, [C.c_int]),
     "dn_augment_batch": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dn_sgd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "dn_grad_norm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "dn_sgd_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, SgdHyper, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -9,8 +9,13 @@ turns the records into the list `CocoEvaluator.prepare_for_coco_detection` build
 `evalrec.voc_mean_ap` scores them the PASCAL VOC way. `evaluate_voc` is the same loop with the scoring on the device: the detections stay
 there and only the mAP comes back (demonet_amd/voceval.py). `evaluate_coco` is that loop with pycocotools' matching and its twelve numbers
 (demonet_amd/cocoeval.py).
+
+`train_one_epoch` is the reference's training loop (demonet/engine.py:14-56) for head fine-tuning: with `optim.SGD` the finiteness check of the
+loss runs inside the optimizer's launch and the host reads the device once every `print_freq` steps.
 """
 import collections
+import functools
+import math
 import time
 from typing import Dict, Iterable, List, Tuple
 
@@ -182,6 +187,123 @@ def evaluate_coco(model, data_loader: Iterable, device="cuda:0", depth: int = 3,
     dt = t1 - t_start
     return summary, {"images": n_images, "seconds": dt, "images_per_sec": n_images / max(dt, 1e-9), "model_seconds": model_time,
                      "summarize_seconds": t1 - t0}
+
+
+def _warmup(optimizer, n_batches: int):
+    """The LR ramp of epoch 0: the rate climbs linearly from 1/1000 of its value to the whole of it over w = min(1000, n_batches - 1) scheduler
+    steps and stays there (the reference's factor 1e-3 (1 - x/w) + x/w, engine.py:21-25, in its affine form)."""
+    w = min(1000, n_batches - 1)
+    return torch.optim.lr_scheduler.LambdaLR(optimizer, lambda x: 1.0 if x >= w else 1e-3 + (1.0 - 1e-3) * x / w)
+
+
+class TrainLog:
+    """What train_one_epoch returns: meters[name] = the list of per-step floats ("loss", every loss term, "lr" and, when the optimizer computes
+    it, "grad_norm"); global_avg = {name: mean over the steps}."""
+
+    def __init__(self):
+        self.meters: Dict[str, List[float]] = collections.OrderedDict()
+
+    def update(self, **values):
+        for k, v in values.items():
+            self.meters.setdefault(k, []).append(float(v))
+
+    @property
+    def global_avg(self) -> Dict[str, float]:
+        return {k: sum(v) / len(v) for k, v in self.meters.items() if v}
+
+    def line(self, names=None) -> str:
+        """the last value and the mean of every meter, for a progress line"""
+        return "  ".join("{}: {:.4g} ({:.4g})".format(k, v[-1], sum(v) / len(v)) for k, v in self.meters.items() if v and (names is None or k in names))
+
+    def __str__(self):
+        return self.line()
+
+
+def train_one_epoch(model, optimizer, data_loader, device, epoch, print_freq, preset=None, generator=None) -> TrainLog:
+    """The reference's train_one_epoch (engine.py:14-56): model.train(); on epoch 0 a linear LR warm-up from 1/1000 over
+    min(1000, len(data_loader) - 1) iterations; per batch the loss dict of `model(images, targets)`, its sum, zero_grad, backward, optimizer step,
+    scheduler step. data_loader yields (images, targets) and has a length. preset (e.g. model.train_preset()): images, targets =
+    preset(images, targets, generator) first -- decoded uint8 images of any sizes to the network's input; without it the images are moved to
+    `device` as they are, the targets' tensors with them. Returns a TrainLog; its "lr" is the rate each step used (the reference logs the rate
+    after the scheduler's step, i.e. the next step's).
+
+    With a demonet_amd.optim.SGD the loop does not wait for the device between log points: the loss terms gate the optimizer's launch (a step whose
+    loss is not finite, and every step after it, writes nothing), every step's loss terms, their sum and the gradient norm go into a ring on the
+    device, and the ring and the gate are read once every print_freq steps and once at the end. A tripped gate then raises FloatingPointError
+    naming the step and its loss terms; parameters and momentum buffers are as of the last good step. The reference stops AT the first bad step
+    (engine.py:41-44); this loop notices within print_freq steps, having changed nothing in between.
+    With any other optimizer the loss is checked on the host every step, as the reference does (FloatingPointError instead of sys.exit)."""
+    from .optim import SGD
+    device = torch.device(device)
+    print_freq = max(int(print_freq), 1)
+    model.train()
+    log = TrainLog()
+    n_batches = len(data_loader)
+    tag = f"epoch {epoch}"
+    ramp = _warmup(optimizer, n_batches) if epoch == 0 else None
+    ours = isinstance(optimizer, SGD)
+    ring = None             # [print_freq][2 + terms] fp32 on the device: grad norm, loss terms, sum
+    names: List[str] = []
+    window: List[Tuple[int, float]] = []       # (iteration, lr) of the steps in the ring
+    first_opt_step = optimizer.steps if ours else 0
+
+    def read(i_last):
+        host = ring[:len(window)].cpu()
+        tripped, at = optimizer.status()
+        bad = at - first_opt_step if tripped else None          # the iteration of the step that tripped the gate
+        for row, (it, lr) in zip(host.tolist(), window):
+            if bad is not None and it >= bad:
+                if it == bad:
+                    raise FloatingPointError("Loss is {} at step {} of epoch {}, stopping training: {} (parameters and momentum are those of step {})".format(
+                        row[-1], it, epoch, dict(zip(names, row[1:-1])), it - 1))
+                break
+            log.update(loss=row[-1], **dict(zip(names, row[1:-1])))
+            log.update(lr=lr)
+            if optimizer.grad_norm is not None:
+                log.update(grad_norm=row[0])
+        if bad is not None:      # tripped by a step of an earlier window or of another caller
+            raise FloatingPointError("the optimizer's gate tripped at its step {}, before iteration {} of epoch {}".format(at, window[0][0], epoch))
+        window.clear()
+        print(f"{tag}  step {i_last + 1}/{n_batches}  {log.line()}", flush=True)
+
+    for i, (images, targets) in enumerate(data_loader):
+        if preset is not None:
+            images, targets = preset([image.to(device) for image in images], targets, generator)
+        else:
+            images = [im.to(device) for im in images]
+            targets = [{k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in t.items()} for t in targets]
+        loss_dict = model(images, targets)
+        terms = list(loss_dict.values())
+        losses = functools.reduce(torch.add, terms)
+        if ours:
+            if ring is None:
+                names = list(loss_dict)
+                ring = torch.zeros((print_freq, 2 + len(names)), dtype=torch.float32, device=losses.device)
+            row = ring[len(window)]
+            torch.stack([v.detach() for v in terms] + [losses.detach()], out=row[1:])
+            optimizer.zero_grad()
+            losses.backward()
+            optimizer.step(gate=row[1:], norm_out=row[0:1])
+            window.append((i, optimizer.param_groups[0]["lr"]))
+        else:
+            loss_value = losses.item()
+            if not math.isfinite(loss_value):
+                raise FloatingPointError("Loss is {} at step {} of epoch {}, stopping training: {}".format(
+                    loss_value, i, epoch, {k: v.item() for k, v in loss_dict.items()}))
+            optimizer.zero_grad()
+            losses.backward()
+            optimizer.step()
+            log.update(loss=loss_value, **{k: v.item() for k, v in loss_dict.items()})
+            log.update(lr=optimizer.param_groups[0]["lr"])
+            if (i + 1) % print_freq == 0 or i + 1 == n_batches:
+                print(f"{tag}  step {i + 1}/{n_batches}  {log.line()}", flush=True)
+        if ramp is not None:
+            ramp.step()
+        if ours and len(window) == print_freq:
+            read(i)
+    if ours and window:
+        read(n_batches - 1)
+    return log
 
 
 def coco_records(results: Dict[int, Dict[str, torch.Tensor]]) -> List[dict]:

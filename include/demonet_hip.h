@@ -413,6 +413,52 @@ DN_API size_t dn_augment_workspace_bytes(int n);
 DN_API int dn_augment_batch(const uint8_t* const* images, const int32_t* sizes, const int32_t* params, int n, int out_h, int out_w,
                             float* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The optimizer step of head fine-tuning on the device (csrc/optim.hip): torch.optim.SGD's update and clip_grad_norm_'s norm for ALL
+ * tensors of a param group in one launch each, and the reference loop's `math.isfinite(loss)` (engine.py:39-44) as a gate inside the update launch,
+ * so that a training loop needs no host synchronisation per step. fp32 tensors only.
+ * table_dev: DEVICE memory, T records dn_sgd_tensor and, right behind them, int32 first[T + 1]: first[t] = the number of chunks of the tensors in
+ * front of t, a chunk = DN_SGD_CHUNK consecutive elements of one tensor (ceil(numel / DN_SGD_CHUNK) per tensor), first[T] = chunks. p, g and buf
+ * hold numel contiguous floats each; buf (the momentum buffer) is read and written only when momentum != 0 and may be null otherwise. The caller
+ * keeps the table true to its tensors: the library cannot see it from the host and reads numel elements at every pointer.
+ * dn_grad_norm: *norm_out_dev = sqrt(sum of g * g over every tensor of the table), fp32. Two launches: per-chunk sums in float64 (an fp32 square is
+ * exact there; fixed order per thread, fixed-shape tree per workgroup) into partials_ws[chunk], then ONE workgroup adds the partials in index order,
+ * takes the square root in float64 and rounds once. No atomics: the same bits on every run. partials_ws: 8-byte aligned, at least
+ * dn_sgd_workspace_bytes(T, chunks) (0 for sizes the calls refuse).
+ * dn_sgd_step: one launch, per element, every operation one rounded fp32 operation (no contraction) in torch.optim.SGD's order:
+ *   d = g * coef                       only when max_norm > 0: coef = min(1, max_norm / (*norm_dev + 1e-6)), clip_grad_norm_'s coefficient
+ *   d = d + weight_decay * p           only when weight_decay != 0
+ *   b = first_step ? d : momentum * b + (1 - dampening) * d       only when momentum != 0
+ *   d = nesterov ? d + momentum * b : b                           only when momentum != 0
+ *   p = p - lr * d
+ * g is NOT modified (clip_grad_norm_ scales .grad in place; here the coefficient is applied on the way). 16-byte accesses where p, g and buf are
+ * 16-byte aligned, 4-byte accesses otherwise; no element at or beyond numel is touched.
+ * The gate: gate_dev = gate_count (0 .. DN_SGD_MAX_GATE) fp32 DEVICE values, typically the loss terms and the norm. If any of them is not finite, or
+ * status_dev[0] != 0, the launch writes nothing to any p or buf and sets status_dev[0] = 1: the gate is sticky, every later call is skipped until
+ * the caller clears status_dev[0]. status_dev: int32 [2] on the device; [1] receives hyper.step from every call that found [0] clear, so after a
+ * trip it holds the step that tripped.
+ * Both calls only enqueue on `stream`. DN_E_INVALID for a null table, status, workspace, norm_out or (with gate_count > 0) gate pointer, T or chunks
+ * < 1, gate_count outside 0 .. DN_SGD_MAX_GATE, a negative or non-finite lr, momentum, weight_decay or max_norm, a non-finite dampening, a negative
+ * step, nesterov without momentum or with dampening, max_norm > 0 without norm_dev; DN_E_UNSUPPORTED for T > 65 535; DN_E_WORKSPACE for a
+ * workspace below dn_sgd_workspace_bytes. */
+#define DN_SGD_CHUNK 2048
+#define DN_SGD_MAX_GATE 8
+typedef struct dn_sgd_tensor {
+    float* p;
+    const float* g;
+    float* buf;
+    int64_t numel;
+} dn_sgd_tensor;
+typedef struct dn_sgd_hyper {
+    float lr, momentum, dampening, weight_decay;
+    int32_t nesterov, first_step;       /* first_step: the buffers of this table's tensors do not exist yet: b = d, without dampening */
+    int32_t step;                       /* the caller's step counter, for status_dev[1] */
+    int32_t reserved;
+} dn_sgd_hyper;
+DN_API size_t dn_sgd_workspace_bytes(int T, int chunks);
+DN_API int dn_grad_norm(const dn_sgd_tensor* table_dev, int T, int chunks, void* partials_ws, size_t workspace_bytes, float* norm_out_dev, void* stream);
+DN_API int dn_sgd_step(const dn_sgd_tensor* table_dev, int T, int chunks, dn_sgd_hyper hyper, const float* gate_dev, int gate_count,
+                       const float* norm_dev, float max_norm, int32_t* status_dev, void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
