@@ -98,6 +98,9 @@ _SIGNATURES = {
     "dn_merge_detections_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "dn_merge_detections": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 6
                             + [C.c_size_t, C.c_void_p]),
+    "dn_fuse_detections_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "dn_fuse_detections": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 6
+                           + [C.c_size_t, C.c_void_p]),
     "dn_match_detections": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [C.POINTER(C.c_double), C.c_int, C.c_double] + [C.c_void_p] * 5),
     "dn_coco_match": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 4 + [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int] + [C.c_void_p] * 5),
     "dn_augment_workspace_bytes": (C.c_size_t, [C.c_int]),

@@ -378,6 +378,20 @@ class SSD(_Tracked):
         from .sliced import detect_sliced
         return detect_sliced(self, images, tile, overlap, full_image, merge_thresh, metric, class_agnostic, max_tiles_per_forward)
 
+    def detect_tta(self, images, hflip: bool = True, fuse: str = "wbf", thresh: Optional[float] = None,
+                   skip_thresh: Optional[float] = None) -> List[Dict[str, Tensor]]:
+        """Horizontal-flip test-time augmentation (demonet_amd/fusion.py): every image is detected twice, as it is and mirrored
+        (torch.flip along the width; the mirrored pass's boxes are mapped back by x1' = W - x2, x2' = W - x1), both passes in one forward_batch,
+        and the two sets of detections are reduced per image on the device. fuse="wbf": weighted boxes fusion (include/demonet_hip.h,
+        dn_fuse_detections): boxes of one label with IoU > thresh are averaged with their scores as weights, and a detection that only one of the
+        passes made keeps half its score; detections below skip_thresh do not take part. fuse="nms": one more hard NMS per class instead
+        (dn_merge_detections). images: an [N, 3, H, W] float tensor in [0, 1] on the GPU or a list of [3, H, W] tensors (sizes may differ: one
+        pass pair per distinct size). thresh defaults to nms_thresh, skip_thresh to score_thresh. Eval mode only.
+        Returns one {"boxes", "scores", "labels"} per image like forward, in the input order, at most detections_per_img each; one device-to-host
+        copy (the counts). ValueError for bad arguments and for hflip=False with fuse="wbf": a single source has nothing to fuse."""
+        from .fusion import detect_tta
+        return detect_tta(self, images, hflip, fuse, thresh, skip_thresh)
+
     def batch_split(self, n: int) -> int:
         """Number of parallel sub-batch launch chains a forward of n images is issued as (1 = a single chain)."""
         if self._handle is None:

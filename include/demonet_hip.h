@@ -314,6 +314,39 @@ DN_API int dn_merge_detections(const float* boxes_dev, const float* scores_dev, 
                                int class_agnostic, int d_out, float* boxes_out_dev, float* scores_out_dev, int64_t* labels_out_dev,
                                int32_t* counts_out_dev, int32_t* src_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Weighted boxes fusion over detections that already exist (csrc/fuse.hip): the reducer for sources that are different opinions about
+ * the same objects -- the plain and the flipped pass of an image, several checkpoints -- where dn_merge_detections' hard NMS would keep one box and
+ * drop what the other sources knew (Solovyev, Wang, Gabruseva 2019; conf_type 'avg' of the ensemble_boxes package). demonet_amd/fusion.py
+ * (fuse_detections, detect_tta, ensemble_detect) is the caller. Inputs as for dn_merge_detections (boxes [S][d][4] fp32, scores [S][d] fp32, labels
+ * [S][d] int64, counts [S] int32, offsets_dev [S][2] fp32, the HOST array group_begin [groups + 1]; sources outside every group are ignored), plus
+ * weights_dev [S] fp32, one weight per source (NULL: every weight is 1). All arithmetic is fp32 with one rounding per operation. Per group:
+ *   1. W = the weights of the group's sources, added in source order starting from 0;
+ *   2. candidates: the rows j < counts[s] of its sources with v = score * weight[s] (one multiplication) not NaN, v >= skip_thresh and v > 0; a
+ *      candidate's box is (x1 + ox, y1 + oy, x2 + ox, y2 + oy), one addition each;
+ *   3. rank: v descending, ties by ascending flattened index s * d + j;
+ *   4. in rank order, a candidate of label l is compared with the clusters of label l in creation order: u = IoU(cluster's fused box, candidate's
+ *      box) in the operation order of dn_merge_detections (DN_MERGE_IOU, the fused box as a_i). It joins the cluster with the largest u > thresh
+ *      (strict; the earliest-created one on a tie; a NaN u never matches);
+ *   5. no such cluster: it opens a new one with T = 1, Sv = v, A_k = v * coord_k, and the fused box is the candidate's box exactly (not A / Sv);
+ *   6. otherwise T += 1, Sv += v, A_k += v * coord_k (multiply, then add), fused coord_k = A_k / Sv;
+ *   7. at the end a cluster's score is ((Sv / float(T)) * min(float(T), W)) / W, evaluated left to right, min(t, W) = W < t ? W : t;
+ *   8. output: the clusters by that score descending (a NaN score, which only weights that are not positive numbers can produce, behind every
+ *      number), ties by creation order; the first d_out of them.
+ * Outputs: boxes_out [groups][d_out][4] (the fused boxes), scores_out [groups][d_out], labels_out [groups][d_out] int64, counts_out [groups] int32
+ * and, optional (may be NULL), members_out [groups][d_out] int32 = T; rows at or beyond the count are zero.
+ * Limits: d and d_out 1 .. 512, at most 8 192 slots (sources * d) per group -- the walk is quadratic when every box is a cluster of its own, which
+ * is why this is narrower than the merge's 65 536 --, s_total * d < 2^31: DN_E_UNSUPPORTED beyond them. DN_E_WORKSPACE below
+ * dn_fuse_detections_workspace_bytes, which takes group_begin as well and is 0 for everything the call refuses on its sizes or its group_begin.
+ * DN_E_INVALID for null pointers (weights_dev and members_out_dev excepted), non-positive sizes, a thresh or skip_thresh that is NaN or negative, a
+ * group_begin that decreases or leaves 0 .. s_total, boxes / boxes_out / workspace not 16-byte aligned, offsets / labels not 8-byte aligned.
+ * group_begin is read during the call only. Six launches per 64 groups, asynchronous on `stream`, no host synchronisation, can be captured;
+ * deterministic (no float atomics: the same bits on every run). */
+DN_API size_t dn_fuse_detections_workspace_bytes(int s_total, int d, const int32_t* group_begin, int groups);
+DN_API int dn_fuse_detections(const float* boxes_dev, const float* scores_dev, const int64_t* labels_dev, const int32_t* counts_dev,
+                              const float* offsets_dev, const float* weights_dev, int s_total, int d, const int32_t* group_begin, int groups,
+                              float thresh, float skip_thresh, int d_out, float* boxes_out_dev, float* scores_out_dev, int64_t* labels_out_dev,
+                              int32_t* counts_out_dev, int32_t* members_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* PASCAL VOC true / false positive marking on the device (csrc/evalmatch.hip): the per-image part of the reference's voc_eval
  * (data/voc_eval.py:116-155) on the arrays dn_forward wrote, for several overlap thresholds in one launch. demonet_amd/voceval.py accumulates the
  * flags and finishes precision / recall / AP; engine.evaluate_voc is the loop around it.
