@@ -74,6 +74,8 @@ _SIGNATURES = {
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "dn_depthwise_conv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dn_depthwise_pool_blocks": (C.c_int, [C.c_int] * 6),
+    "dn_depthwise_conv_pool": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]),
     "dn_dense_conv": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 10 + [C.c_void_p]),
     "dn_expand_depthwise": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 11 + [C.c_void_p]),
     "dn_expand_depthwise_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int]),

@@ -10,8 +10,17 @@
 #ifdef DN_DEV_STAMPS
 static long long* g_se_stamps = nullptr;     // dev build only (tools/probe_se.py)
 extern "C" __attribute__((visibility("default"))) void dn_debug_se_stamps(void* dev_ptr) { g_se_stamps = (long long*)dev_ptr; }
+static long long* g_dw_stamps = nullptr;     // dev build only (tools/probe_dw.py): per-workgroup stamps [image][workgroup][8] of the next dw_kernel launches
+extern "C" __attribute__((visibility("default"))) void dn_debug_dw_stamps(void* dev_ptr) { g_dw_stamps = (long long*)dev_ptr; }
+// (the stamp pointer is a kernel argument of the dev build only: the product kernels keep their signatures)
+#define DW_STAMPS_PARAM , long long* const stamps
+#define DW_STAMPS_ARG(p) , p
+#define DW_STAMP(k) do { if (stamps && threadIdx.x == 0) stamps[((size_t)n * nblocks + bx) * 8 + (k)] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 constexpr long long* g_se_stamps = nullptr;
+#define DW_STAMPS_PARAM
+#define DW_STAMPS_ARG(p)
+#define DW_STAMP(k) do { } while (0)
 #endif
 
 namespace {
@@ -162,10 +171,18 @@ __device__ __forceinline__ bool dw_se_tail_is_small(int c, int sq, int nblk) {
 
 // POOL: 0 = none, 1 = per-workgroup channel sums for the squeeze-excitation, 2 = sums + the FCs in the image's last workgroup
 //   (dw_se_tail: its 16-row load batches need 114 registers, which capped EVERY pooling launch while the code was compiled into all of them).
-template <int K, int S, int TW, int POOL>
-__device__ __forceinline__ void dw_body(const DwArgs& a, const int bx, const int nblocks, const int n) {
-    constexpr int NIN = (TW - 1) * S + K;
-    extern __shared__ float red[];            // [256][8], only when pooling
+// WLDS (DN_DW_WLDS, default on; dw_wlds_bytes): the launch's k x k x c weights and c biases are copied to LDS once per workgroup, group-major
+//   ([c / 8][k * k] 16-byte slots, then the biases), and a lane reads its taps at immediate offsets just in time per row -- instead of 25 (9) global
+//   16-byte loads per strip, each with 64-bit address arithmetic; the input rows come through raw buffer loads whose out-of-range OFFSET is the zero
+//   padding (one 32-bit select per load instead of a 64-bit pointer select). Same taps in the same order through the same v_fma_mix_f32: bit-identical
+//   to WLDS = false, which stays as the knob's other side and the reference of tests/test_gpu_dw_wlds.py.
+template <int K, int S, int TW, int POOL, bool WLDS>
+__device__ __forceinline__ void dw_body(const DwArgs& a, const int bx, const int nblocks, const int n DW_STAMPS_PARAM) {
+    constexpr int NIN = (TW - 1) * S + K, KK = K * K;
+    // !WLDS: red[256][8], only when pooling. WLDS: [KK * c halves: weights][c floats: bias][red]. The SE tail's scratch aliases all of it (dead by then).
+    extern __shared__ __attribute__((aligned(16))) float dw_sh[];
+    float* const red = WLDS ? dw_sh + (KK * a.c) / 2 + a.c : dw_sh;
+    DW_STAMP(0);
     const unsigned C8 = a.c >> 3;
     const unsigned idx0 = bx * 256 + threadIdx.x;
     const unsigned q1 = fd_div(idx0, a.fd_c8);
@@ -174,23 +191,65 @@ __device__ __forceinline__ void dw_body(const DwArgs& a, const int bx, const int
     const unsigned oy = fd_div(q1, a.fd_xs);
     const unsigned xs = q1 - oy * a.fd_xs.d;
     const bool valid = (int)oy < a.ho;
-    if (!valid && POOL == 0) return;
+    if (!valid && POOL == 0 && !WLDS) return;       // (WLDS: every thread copies and meets the barrier)
     const int ox0 = xs * TW;
     const unsigned c0 = cg * 8;
+    const int ix0 = ox0 * S - a.pad;
     float psum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    half8 xin[2][NIN];
+    // WLDS: the image as a raw buffer of h * w * c * 2 bytes (< 2^31: dw_wlds_bytes). A request whose offset is 0x80000000 lies outside as a whole and
+    // returns zeros without an access -- the select is on the offset, never a computed negative one (that could land inside the previous row).
+    const unsigned c2 = (unsigned)a.c * 2u;
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.x + (size_t)n * a.h * a.w_ * a.c), 0, WLDS ? a.h * a.w_ * a.c * 2 : 0, 0x00020000);
+    auto load_row_buf = [&](const int ky, const int buf) {
+        const int iy = (int)oy * S - a.pad + ky;
+        const bool yok = valid && (unsigned)iy < (unsigned)a.h;
+        const unsigned rowoff = (unsigned)((iy * a.w_ + ix0) * a.c + (int)c0) * 2u;       // (may wrap below zero for the left padding: only offsets of taps inside the image are used)
+#pragma unroll
+        for (int i = 0; i < NIN; ++i) {
+            const bool ok = yok && (unsigned)(ix0 + i) < (unsigned)a.w_;
+            xin[buf][i] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(xrs, ok ? rowoff + (unsigned)i * c2 : 0x80000000u, 0, 0));
+        }
+    };
+    if constexpr (WLDS) {
+        load_row_buf(0, 0);         // the first row's round trip runs under the copy's
+        // weights [KK][c] -> group-major slots: item i = tap * C8 + group is the i-th 16 bytes of the source. Clamped, not predicated, batches of 4.
+        const uint4* const wsrc = reinterpret_cast<const uint4*>(a.w);
+        uint4* const wdst = reinterpret_cast<uint4*>(dw_sh);
+        const unsigned nitems = KK * C8;
+        // (i / C8 without fd_div's uniform `d > 1` select: hipcc turns that into a branch per item, and every load then waits alone in front of its store)
+        const unsigned one = a.fd_c8.d == 1 ? ~0u : 0u;
+        // the biases (c <= 1024: one clamped float4 per thread), requested in front of the weights so that their round trip is not one of its own
+        float4* const bdst = reinterpret_cast<float4*>(dw_sh + (KK * a.c) / 2);
+        const unsigned bi = min(threadIdx.x, ((unsigned)a.c >> 2) - 1);
+        const float4 bv = reinterpret_cast<const float4*>(a.bias)[bi];
+        for (unsigned i0 = threadIdx.x; i0 < nitems; i0 += 1024) {
+            uint4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = wsrc[min(i0 + u * 256, nitems - 1)];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {       // (a clamped item rewrites the last slot with its own value: no branch between the loads)
+                const unsigned i = min(i0 + u * 256, nitems - 1), tap = __umulhi(i, a.fd_c8.m) + (i & one);       // (m == 0 for d == 1)
+                wdst[(i - tap * C8) * KK + tap] = v[u];
+            }
+        }
+        bdst[bi] = bv;
+        __syncthreads();
+    }
+    DW_STAMP(1);
     if (valid) {
 
     float acc[TW][8];
     {
-        const float4 b0 = *reinterpret_cast<const float4*>(a.bias + c0);
-        const float4 b1 = *reinterpret_cast<const float4*>(a.bias + c0 + 4);
+        const float* const bsrc = WLDS ? dw_sh + (KK * a.c) / 2 : a.bias;
+        const float4 b0 = *reinterpret_cast<const float4*>(bsrc + c0);
+        const float4 b1 = *reinterpret_cast<const float4*>(bsrc + c0 + 4);
 #pragma unroll
         for (int t = 0; t < TW; ++t) {
             acc[t][0] = b0.x; acc[t][1] = b0.y; acc[t][2] = b0.z; acc[t][3] = b0.w;
             acc[t][4] = b1.x; acc[t][5] = b1.y; acc[t][6] = b1.z; acc[t][7] = b1.w;
         }
     }
-    const int ix0 = ox0 * S - a.pad;
     typedef const __attribute__((address_space(1))) half8* gp8;     // explicit global pointers: the selected pointer must not degrade to a flat load
     const gp8 zero = (gp8)(&g_dw_zero16);
     // Software-pipelined rows: two register sets; row ky + 1 is requested BEFORE the multiply-adds of row ky are issued, so only the first row's
@@ -203,8 +262,7 @@ __device__ __forceinline__ void dw_body(const DwArgs& a, const int bx, const int
     const half_t* const wbase = a.w + c0;
     const half_t* const xbase = a.x + (size_t)n * a.h * a.w_ * a.c + c0;
     half8 wv[2][K];
-    half8 xin[2][NIN];
-    auto load_row = [&](const int ky, const int buf) {
+    auto load_row_ptr = [&](const int ky, const int buf) {
         const int iy = (int)oy * S - a.pad + ky;
         const bool yok = iy >= 0 && iy < a.h;
 #pragma unroll
@@ -217,20 +275,47 @@ __device__ __forceinline__ void dw_body(const DwArgs& a, const int bx, const int
             xin[buf][i] = *(ok ? (gp8)(rowp + (unsigned)(ix * a.c)) : zero);
         }
     };
-    load_row(0, 0);
+    auto load_row = [&](const int ky, const int buf) {
+        if constexpr (WLDS) load_row_buf(ky, buf);
+        else load_row_ptr(ky, buf);
+    };
+    const uint4* const wl = reinterpret_cast<const uint4*>(dw_sh) + cg * KK;        // WLDS: this lane's taps
+    if constexpr (!WLDS) load_row(0, 0);
 #pragma unroll
     for (int ky = 0; ky < K; ++ky) {
         if (ky + 1 < K) load_row(ky + 1, (ky + 1) & 1);
+        if constexpr (WLDS) {
+            // taps from LDS just in time; per output the taps still run in (ky, kx) order
 #pragma unroll
-        for (int t = 0; t < TW; ++t)
+            for (int kx = 0; kx < K; ++kx) {
+                const uint4 w = wl[ky * K + kx];
 #pragma unroll
-            for (int kx = 0; kx < K; ++kx)
-                fma_mix_h8(acc[t], *reinterpret_cast<const uint4*>(&xin[ky & 1][t * S + kx]), *reinterpret_cast<const uint4*>(&wv[ky & 1][kx]));
+                for (int t = 0; t < TW; ++t) fma_mix_h8(acc[t], *reinterpret_cast<const uint4*>(&xin[ky & 1][t * S + kx]), w);
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < TW; ++t)
+#pragma unroll
+                for (int kx = 0; kx < K; ++kx)
+                    fma_mix_h8(acc[t], *reinterpret_cast<const uint4*>(&xin[ky & 1][t * S + kx]), *reinterpret_cast<const uint4*>(&wv[ky & 1][kx]));
+        }
     }
+    DW_STAMP(2);
     half_t* orow = a.out + ((size_t)(n * a.ho + oy) * a.wo) * a.c + c0;
+    int ox0s = ox0;
+    if constexpr (POOL != 0 && !WLDS) {
+        // the strip's first output column again, from the thread index (which the pooling below keeps alive anyway): held across the row loop it was
+        // the one value too many at the 128- / 168-register caps of these instantiations (a 4-byte spill)
+        // (the empty asm does nothing but hide from hipcc that t2 is the thread index: without it the recomputation is merged with the value computed in
+        //  front of the row loop and that value is kept -- and spilled -- again. tests/test_dw_wlds_isa.py holds the result: no scratch.)
+        unsigned t2 = threadIdx.x;
+        asm volatile("" : "+v"(t2));
+        const unsigned q2 = fd_div(bx * 256 + t2, a.fd_c8);
+        ox0s = (int)(q2 - fd_div(q2, a.fd_xs) * a.fd_xs.d) * TW;
+    }
 #pragma unroll
     for (int t = 0; t < TW; ++t) {
-        if (ox0 + t >= a.wo) break;
+        if (ox0s + t >= a.wo) break;
         dn_act_n<float[8], 8>(acc[t], a.act);
         half8 o;
 #pragma unroll
@@ -238,9 +323,10 @@ __device__ __forceinline__ void dw_body(const DwArgs& a, const int bx, const int
             if constexpr (POOL != 0) psum[e] += acc[t][e];
             o[e] = (half_t)acc[t][e];
         }
-        *reinterpret_cast<half8*>(orow + (unsigned)((ox0 + t) * a.c)) = o;
+        *reinterpret_cast<half8*>(orow + (unsigned)((ox0s + t) * a.c)) = o;
     }
     }   // valid
+    DW_STAMP(3);
     if constexpr (POOL != 0) {
         // SE squeeze (mobilenetv3.py:32 adaptive_avg_pool2d) fused as deterministic per-workgroup partial sums:
         // threads with equal channel group sit C8 apart; thread t < C8 adds them in a fixed order.
@@ -278,24 +364,27 @@ __device__ __forceinline__ void dw_body(const DwArgs& a, const int bx, const int
             // rows back with device-scope atomic loads issued after its ticket has returned (the barrier below). This is the
             // hardware's ordering, spelled out -- the formal-model release would be the flushing fence.
             __shared__ int s_last;
+            DW_STAMP(4);
             __syncthreads();
             if (threadIdx.x == 0)
                 s_last = __hip_atomic_fetch_add(&a.se_counter[n], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(nblocks - 1);
             __syncthreads();
+            DW_STAMP(5);
             if (s_last) {
-                if (dw_se_tail_is_small(a.c, a.se_sq, nblocks)) dw_se_tail_small(a, n, nblocks, red);
-                else dw_se_tail(a, n, nblocks, red);
+                if (dw_se_tail_is_small(a.c, a.se_sq, nblocks)) dw_se_tail_small(a, n, nblocks, dw_sh);
+                else dw_se_tail(a, n, nblocks, dw_sh);
                 if (threadIdx.x == 0) a.se_counter[n] = 0u;
+                DW_STAMP(6);
             }
         }
     }
 }
 
-template <int K, int S, int TW, int POOL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 3 ? 4 : 3))) void dw_kernel(DwArgs a, int nblocks) {
+template <int K, int S, int TW, int POOL, bool WLDS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 3 || WLDS ? 4 : 3))) void dw_kernel(DwArgs a, int nblocks DW_STAMPS_PARAM) {
     int img, bx;
     if (!xcd_image_of2(a.xq, a.n, img, bx)) return;
-    dw_body<K, S, TW, POOL>(a, bx, nblocks, img);
+    dw_body<K, S, TW, POOL, WLDS>(a, bx, nblocks, img DW_STAMPS_ARG(stamps));
 }
 
 // Grouped launch: up to 12 independent depthwise problems of the same (k, stride) and batch in ONE launch (the head
@@ -320,7 +409,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 3 ? 4 
     if (a.xq > 0) { img = (rel & 7) * a.xq + blockIdx.y; bx = rel >> 3; }
     else { img = blockIdx.y; bx = rel; }
     if (img >= a.n) return;
-    dw_body<K, S, TW, 0>(a, bx, g.nblocks[p], img);
+    dw_body<K, S, TW, 0, false>(a, bx, g.nblocks[p], img DW_STAMPS_ARG(nullptr));
 }
 
 // what the launcher fills in, and whether the problem lies inside the kernel's index range
@@ -332,6 +421,22 @@ bool dw_fill(DwArgs& a, const int tw) {
     return fd_ok(threads, c8) && fd_ok(threads / c8 + 1, xs) && (unsigned long long)a.h * a.w_ * a.c < 0x80000000ull;
 }
 int dw_blocks(const DwArgs& a, const int tw) { return dn_cdiv((long)a.ho * ((a.wo + tw - 1) / tw) * (a.c / 8), 256); }      // workgroups per image
+
+// DN_DW_WLDS (read per launch): LDS bytes of the weight + bias image of dw_body<.., WLDS = true>, or 0 for the per-thread weight loads.
+//   1 (default): launches of at most 128 channels -- the copy is then at most two 16-byte loads per thread and a workgroup's 256 strips replace
+//      6400 (2304) weight loads by <= 400 (144); measured (profiles/dw_wlds_ab.txt): 72 / 120 channels on 80 x 80 / 40 x 40 maps -2 to -3 us per launch with
+//      and without the SE tail, 32 channels on 150 x 150 -11 %. Wider launches (480 - 960 channels on 20 x 20 / 10 x 10 maps) pay for a copy of 24 - 34 KB
+//      per workgroup and its barrier in front of every workgroup's first row: +0.4 to +2.3 us, so they keep the per-thread loads;
+//   2: wherever the image fits (A/B runs and tests/test_gpu_dw_wlds.py): at most 1024 channels (one bias float4 per thread), 64 KB with red[] (5 x 5 x 1024
+//      channels + bias + red[] = 62 KB does), a buffer below 2^31 bytes (the out-of-range offset must lie outside it), copy indices inside the fast division;
+//   0: never (the reference of the bit-identity tests).
+size_t dw_wlds_bytes(const DwArgs& a, const int k) {
+    const int knob = dn_knob("DN_DW_WLDS", 1);
+    if (knob == 0 || (knob != 2 && a.c > 128)) return 0;
+    const size_t bytes = (size_t)k * k * a.c * 2 + (size_t)a.c * 4;
+    const bool ok = a.c <= 1024 && bytes + 256 * 8 * 4 <= 64 * 1024 && (unsigned long long)a.h * a.w_ * a.c < 0x40000000ull && fd_ok((unsigned long long)k * k * (a.c / 8) + 1024, a.c / 8);
+    return ok ? bytes : 0;
+}
 
 // DwChoice -> <K, S, TW>: the one table of instantiations (choice.h dw_choose admits exactly these; dw_tw states TW)
 template <int K_, int S_>
@@ -371,12 +476,21 @@ int launch_dw(const DwArgs& a0, const DwChoice::Pool pool, hipStream_t s) {
     dn_note_kernel("dw_kernel<%d,%d,%d>", K, S, TW);
     const int nblocks = dw_blocks(a, TW);
     const dim3 grid = xcd_grid2(nblocks, a.xq, a.n);
+    const size_t red = (size_t)256 * 8 * 4, tail = (size_t)(a.c + a.se_sq + 2048) * 4;
+    const size_t wl = dw_wlds_bytes(a, K);          // 0: the per-thread weight loads
     switch (pool) {
-        case DwChoice::NO_POOL: hipLaunchKernelGGL((dw_kernel<K, S, TW, 0>), grid, dim3(256), 0, s, a, nblocks); break;
-        case DwChoice::POOLED: hipLaunchKernelGGL((dw_kernel<K, S, TW, 1>), grid, dim3(256), (size_t)256 * 8 * 4, s, a, nblocks); break;
+        case DwChoice::NO_POOL:
+            if (wl) hipLaunchKernelGGL((dw_kernel<K, S, TW, 0, true>), grid, dim3(256), wl, s, a, nblocks DW_STAMPS_ARG(g_dw_stamps));
+            else hipLaunchKernelGGL((dw_kernel<K, S, TW, 0, false>), grid, dim3(256), 0, s, a, nblocks DW_STAMPS_ARG(g_dw_stamps));
+            break;
+        case DwChoice::POOLED:
+            if (wl) hipLaunchKernelGGL((dw_kernel<K, S, TW, 1, true>), grid, dim3(256), wl + red, s, a, nblocks DW_STAMPS_ARG(g_dw_stamps));
+            else hipLaunchKernelGGL((dw_kernel<K, S, TW, 1, false>), grid, dim3(256), red, s, a, nblocks DW_STAMPS_ARG(g_dw_stamps));
+            break;
         case DwChoice::POOLED_SE:
             DN_REQUIRE(a.pool && a.se_counter && depthwise_se_tail_supported(a.c, a.se_sq), "depthwise: squeeze-excitation tail needs the pooled output and c <= 1024, squeeze <= 256, both multiples of 8");
-            hipLaunchKernelGGL((dw_kernel<K, S, TW, 2>), grid, dim3(256), (size_t)(a.c + a.se_sq + 2048) * 4, s, a, nblocks);
+            if (wl) hipLaunchKernelGGL((dw_kernel<K, S, TW, 2, true>), grid, dim3(256), std::max(wl + red, tail), s, a, nblocks DW_STAMPS_ARG(g_dw_stamps));
+            else hipLaunchKernelGGL((dw_kernel<K, S, TW, 2, false>), grid, dim3(256), tail, s, a, nblocks DW_STAMPS_ARG(g_dw_stamps));
             break;
     }
     return DN_OK;

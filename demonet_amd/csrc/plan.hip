@@ -1597,3 +1597,36 @@ extern "C" int dn_depthwise_conv(const void* x, const void* w, const float* bias
     DN_HIP_CHECK(hipGetLastError());
     return DN_OK;
 }
+
+extern "C" int dn_depthwise_pool_blocks(int h, int wd, int c, int k, int stride, int pad) {
+    DwArgs a{};
+    a.n = 1; a.h = h; a.w_ = wd; a.c = c; a.k = k; a.stride = stride; a.pad = pad;
+    a.ho = (h + 2 * pad - k) / stride + 1;
+    a.wo = (wd + 2 * pad - k) / stride + 1;
+    return depthwise_pool_blocks(a);
+}
+
+extern "C" int dn_depthwise_conv_pool(const void* x, const void* w, const float* bias, void* out, int n, int h, int wd, int c, int k,
+                                      int stride, int pad, int act, float* pool, const void* se_w1t, const float* se_b1, const void* se_w2t,
+                                      const float* se_b2, float* se_scale, unsigned* se_counter, int squeeze, void* stream) {
+    DN_REQUIRE(x && w && bias && out && pool, "dn_depthwise_conv_pool: null argument");
+    DN_REQUIRE(!se_scale || (se_w1t && se_b1 && se_w2t && se_b2 && se_counter), "dn_depthwise_conv_pool: the squeeze-excitation tail needs both FCs and the counters");
+    DwArgs a;
+    a.x = reinterpret_cast<const half_t*>(x); a.w = reinterpret_cast<const half_t*>(w); a.bias = bias;
+    a.out = reinterpret_cast<half_t*>(out);
+    a.n = n; a.h = h; a.w_ = wd; a.c = c; a.k = k; a.stride = stride; a.pad = pad; a.act = act;
+    a.ho = (h + 2 * pad - k) / stride + 1;
+    a.wo = (wd + 2 * pad - k) / stride + 1;
+    a.xq = xcd_images_per_group(n);
+    a.pool = pool;
+    if (se_scale) {
+        a.se_w1t = reinterpret_cast<const half_t*>(se_w1t); a.se_b1 = se_b1;
+        a.se_w2t = reinterpret_cast<const half_t*>(se_w2t); a.se_b2 = se_b2;
+        a.se_scale = se_scale; a.se_counter = se_counter; a.se_sq = squeeze;
+        a.se_inv = 1.0f / (float)(a.ho * a.wo);
+    }
+    int rc = launch_depthwise(a, reinterpret_cast<hipStream_t>(stream));
+    if (rc) return rc;
+    DN_HIP_CHECK(hipGetLastError());
+    return DN_OK;
+}

@@ -180,6 +180,15 @@ DN_API int dn_dense_conv(const void* x_dev, const void* w_dev, const float* bias
 /* x: [n][h][w][c] fp16, w: [k*k][c] fp16, bias fp32 [c], out [n][ho][wo][c] fp16 */
 DN_API int dn_depthwise_conv(const void* x_dev, const void* w_dev, const float* bias_dev, void* out_dev,
                       int n, int h, int w, int c, int k, int stride, int pad, int act, void* stream);
+/* The same launch with the squeeze-excitation pooling: pool_dev [n][blocks][c] fp32 receives the per-workgroup channel sums of the
+ * outputs, blocks = dn_depthwise_pool_blocks(...). With se_scale_dev non-NULL the last workgroup of each image also runs the FCs
+ * (w1t [c][squeeze], w2t [squeeze][c] fp16, transposed; biases fp32) and writes scale [n][c] fp32; se_counter_dev: n zeroed
+ * unsigneds, left at zero. */
+DN_API int dn_depthwise_pool_blocks(int h, int w, int c, int k, int stride, int pad);
+DN_API int dn_depthwise_conv_pool(const void* x_dev, const void* w_dev, const float* bias_dev, void* out_dev,
+                      int n, int h, int w, int c, int k, int stride, int pad, int act, float* pool_dev,
+                      const void* se_w1t_dev, const float* se_b1_dev, const void* se_w2t_dev, const float* se_b2_dev,
+                      float* se_scale_dev, unsigned* se_counter_dev, int squeeze, void* stream);
 
 /* Fused inverted-residual stages (expdw.hip): [1x1 expand w1/b1 + act1] -> depthwise kxk wd/bd + act2 -> [1x1 project w3/b3
  * (+ residual = x)], BN folded, padding (k-1)/2; replaces the ConvBNActivation chain of InvertedResidual.forward
