@@ -37,6 +37,12 @@ class SgdHyper(C.Structure):
                 ("nesterov", C.c_int32), ("first_step", C.c_int32), ("step", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TrackParams(C.Structure):
+    _fields_ = [("track_thresh", C.c_float), ("low_thresh", C.c_float), ("new_thresh", C.c_float),
+                ("match_thresh", C.c_float), ("second_thresh", C.c_float), ("unconfirmed_thresh", C.c_float),
+                ("track_buffer", C.c_int32), ("class_agnostic", C.c_int32), ("max_tracks", C.c_int32), ("reserved", C.c_int32)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("n_tensors", C.c_int32), ("n_ops", C.c_int32),
                 ("tensors", C.POINTER(TensorDesc)), ("ops", C.POINTER(OpDesc)),
@@ -110,6 +116,9 @@ _SIGNATURES = {
     "dn_sgd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "dn_grad_norm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "dn_sgd_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, SgdHyper, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "dn_track_state_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "dn_track_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dn_track_update": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(TrackParams), C.c_void_p, C.c_size_t] + [C.c_void_p] * 8),
 }
 EXPORTS = tuple(_SIGNATURES)
 

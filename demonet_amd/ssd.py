@@ -392,6 +392,14 @@ class SSD(_Tracked):
         from .fusion import detect_tta
         return detect_tta(self, images, hflip, fuse, thresh, skip_thresh)
 
+    def track(self, images: Tensor, tracker):
+        """Detect and track one frame of every stream (demonet_amd/track.py): forward_batch on images [B, 3, H, W], image b being the
+        current frame of stream b, then tracker.update (a ByteTracker with B streams on the same device) on the detections where they lie: one
+        more launch behind the forward, no device-to-host copy. Returns what ByteTracker.update returns: padded device tensors (boxes [B, T, 4],
+        scores, labels, ids, det [B, T], counts [B], det_ids [B, D]) of the confirmed tracks seen in this frame. Eval mode only."""
+        from .track import track
+        return track(self, images, tracker)
+
     def batch_split(self, n: int) -> int:
         """Number of parallel sub-batch launch chains a forward of n images is issued as (1 = a single chain)."""
         if self._handle is None:

@@ -501,6 +501,78 @@ DN_API int dn_grad_norm(const dn_sgd_tensor* table_dev, int T, int chunks, void*
 DN_API int dn_sgd_step(const dn_sgd_tensor* table_dev, int T, int chunks, dn_sgd_hyper hyper, const float* gate_dev, int gate_count,
                        const float* norm_dev, float max_norm, int32_t* status_dev, void* stream);
 
+/* Multi-object tracking on the device (csrc/track.hip): ByteTrack (Zhang et al. 2022, BYTETracker.update with its constant-velocity
+ * Kalman filter) for `streams` independent video streams, ONE launch per frame step, all tracker state on the device. demonet_amd/track.py
+ * (ByteTracker, SSD.track) is the caller. The frame counter and the id counter live in the state, so a step's arguments do not change from frame to
+ * frame and the call can be captured. Two deviations from the published tracker:
+ *   A. association is GREEDY, not lapjv: pairs above the gate are taken in the total order (IoU descending, track slot ascending, detection row
+ *      ascending), a pair being taken when neither side is taken yet. (An optimal assignment is not unique under ties and cannot be held bit for
+ *      bit; greedy equals it whenever objects do not compete.) The kernel reaches the same matching by rounds of mutually-best pairs;
+ *   B. ids come from a per-stream counter: they start at 1 and are handed out in detection-row order within a frame, so streams are independent
+ *      and the result is deterministic. fuse_score (the MOT20 option) is left out.
+ * The filter. ByteTrack's 8 x 8 filter is four independent two-state filters: the initial covariance, Q and R are diagonal and F couples each
+ * coordinate only with its own velocity, so the covariance stays block-diagonal. Per track and per coordinate k of (cx, cy, a = w / h, h) the state
+ * keeps five floats x, v, Pxx, Pxv, Pvv. All arithmetic is fp32, one rounding per operation, in exactly this order; wp = 0.05f, wv = 0.00625f (1 / 20
+ * and 1 / 160 rounded to fp32), H = the track's x of coordinate h at the moment named:
+ *   box -> measurement: w = x2 - x1, h = y2 - y1, z = (x1 + w * 0.5, y1 + h * 0.5, w / h, h);
+ *   mean -> box: h = x_h, w = x_a * h, x1 = x_cx - w * 0.5, y1 = x_cy - h * 0.5, box = (x1, y1, x1 + w, y1 + h);
+ *   init from z (H = z_h): x = z, v = 0, Pxv = 0, sp = wp * H, sv = wv * H, Pxx = (2 * sp) * (2 * sp), Pvv = (10 * sv) * (10 * sv); for a:
+ *     Pxx = 1e-2f * 1e-2f, Pvv = 1e-5f * 1e-5f;
+ *   predict (H before the step): sp = wp * H, sv = wv * H, qp = sp * sp, qv = sv * sv (for a: 1e-2f * 1e-2f and 1e-5f * 1e-5f); per coordinate, from the
+ *     old values: x = x + v, Pxx = ((Pxx + 2 * Pxv) + Pvv) + qp, Pxv = Pxv + Pvv, Pvv = Pvv + qv;
+ *   update with z (H = the track's current, i.e. predicted, h): sp = wp * H, r = sp * sp (for a: 1e-1f * 1e-1f); per coordinate, from the old values:
+ *     S = Pxx + r, kx = Pxx / S, kv = Pxv / S, y = z - x, x = x + kx * y, v = v + kv * y, Pxx = Pxx - (kx * S) * kx, Pxv = Pxv - (kx * S) * kv,
+ *     Pvv = Pvv - (kv * S) * kv.
+ * A frame step, per stream (slot states: 0 free, 1 tentative, 2 tracked, 3 lost):
+ *   1. frame += 1;
+ *   2. candidates: the rows j < min(max(counts[b], 0), d) whose score is not NaN, whose four coordinates are finite and whose w = x2 - x1 and
+ *      h = y2 - y1 are > 0. HIGH: score >= track_thresh. LOW: low_thresh < score < track_thresh;
+ *   3. every tracked and lost track is predicted, a lost one with the v of h set to 0 first; tentative tracks are not predicted. A track's box in
+ *      the stages below is mean -> box of what it holds then;
+ *   4. stage 1: tracked and lost tracks against the HIGH candidates. A pair is admissible when u > 1 - match_thresh (one fp32 subtraction; strict;
+ *      a NaN u never matches) and the labels are equal (any labels with class_agnostic != 0), u = IoU in the operation order of
+ *      dn_merge_detections (DN_MERGE_IOU, the track's box as a_i): inter = max(0, min x2 - max x1) * max(0, min y2 - max y1),
+ *      u = inter / ((a_i + a_j) - inter). Greedy as in A. A match updates the filter with the row's measurement, sets score = the row's score,
+ *      last_frame = frame, det = the row, state = tracked (a lost track is tracked again and keeps its id);
+ *   5. stage 2: the tracks that were tracked when the frame began and are still unmatched (not the lost ones) against the LOW candidates, gate
+ *      u > 1 - second_thresh, same rules. Those still unmatched become lost;
+ *   6. stage 3: tentative tracks against the HIGH candidates no track has taken, gate u > 1 - unconfirmed_thresh. A match confirms the track
+ *      (state tracked). An unmatched tentative track is removed;
+ *   7. every HIGH candidate still untaken with score >= new_thresh starts a track, in row order, in the lowest free slot (slots freed in step 6
+ *      included, those of step 8 not): id = next_id, next_id += 1, label and score the row's, start_frame = last_frame = frame, det = the row,
+ *      state tentative -- tracked at once when frame == 1. With no free slot the row starts nothing and `dropped` goes up by one;
+ *   8. a lost track with frame - last_frame > track_buffer is removed;
+ *   9. outputs: the tracked tracks with last_frame == frame, in ascending slot order: boxes_out [streams][max_tracks][4] (mean -> box), scores_out,
+ *      labels_out int64, ids_out int64, det_out int32 (the row that updated or started the track), counts_out [streams] int32; rows at or beyond
+ *      the count are zero, det -1. det_ids_out [streams][d] int64, aligned with the input rows: the id of the track output in this frame that the
+ *      row updated or started, or -1.
+ * The state, dn_track_state_bytes(streams, max_tracks) bytes, 16-byte aligned: per stream W = 4 + 28 Tp 4-byte words, Tp = max_tracks rounded up to
+ * a multiple of 4, streams back to back. Words 0 .. 3: int32 frame, next_id, dropped, reserved (0). Then per-slot arrays of Tp entries each, in
+ * this order: int32 state, int32 id, int64 label, fp32 score, fp32 filter [20][Tp] (row 5 k + (0 x, 1 v, 2 Pxx, 3 Pxv, 4 Pvv) for coordinate k of cx, cy,
+ * a, h), int32 start_frame, int32 last_frame, int32 det (the row that updated the slot in the last step, -1 if none did). Every field of a free slot
+ * and of the slots max_tracks .. Tp - 1 is 0. dn_track_reset is one launch: the streams b with which_dev[b] != 0 (which_dev: [streams] uint8 on
+ * the device; NULL: all) restart with frame 0, next_id 1, dropped 0 and an empty table; a new state must be reset before its first step.
+ * params is HOST memory, read during the call only.
+ * Limits: d 1 .. 512, max_tracks 1 .. 256, streams >= 1: DN_E_UNSUPPORTED above them (dn_track_state_bytes then returns 0). DN_E_WORKSPACE for
+ * state_bytes below dn_track_state_bytes. DN_E_INVALID for null pointers (which_dev excepted), non-positive sizes, a threshold that is NaN or
+ * negative, match_thresh / second_thresh / unconfirmed_thresh above 1, a negative track_buffer, boxes / boxes_out / state not 16-byte aligned,
+ * labels / labels_out / ids_out / det_ids_out not 8-byte aligned, the other arrays not 4-byte aligned. One workgroup per stream, no workspace, no
+ * float atomics; asynchronous on `stream`, no host synchronisation, can be captured; deterministic (the same bits on every run). */
+typedef struct dn_track_params {
+    float track_thresh, low_thresh, new_thresh;                 /* ByteTrack: 0.5, 0.1, track_thresh + 0.1 */
+    float match_thresh, second_thresh, unconfirmed_thresh;      /* costs 1 - IoU, as in ByteTrack: 0.8, 0.5, 0.7 */
+    int32_t track_buffer;                                       /* frames a lost track is kept: 30 */
+    int32_t class_agnostic;
+    int32_t max_tracks;                                         /* slots per stream, 1 .. 256 */
+    int32_t reserved;                                           /* 0 */
+} dn_track_params;
+DN_API size_t dn_track_state_bytes(int streams, int max_tracks);
+DN_API int dn_track_reset(void* state_dev, int streams, int max_tracks, const uint8_t* which_dev, void* stream);
+DN_API int dn_track_update(const float* boxes_dev, const float* scores_dev, const int64_t* labels_dev, const int32_t* counts_dev, int streams, int d,
+                           const dn_track_params* params, void* state_dev, size_t state_bytes, float* boxes_out_dev, float* scores_out_dev,
+                           int64_t* labels_out_dev, int64_t* ids_out_dev, int32_t* det_out_dev, int32_t* counts_out_dev, int64_t* det_ids_out_dev,
+                           void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
