@@ -3,6 +3,10 @@
 BatchNorm (eval) is folded here in float64:  w' = w * gamma / sqrt(var + eps),  b' = beta - mean * gamma / sqrt(var + eps)
 (+ conv bias carried through). Weights are stored fp16 in the layouts the kernels read directly (see
 include/demonet_hip.h, dn_op_desc); biases stay fp32, SE FC weights are fp16 (transposed).
+
+What the stored formats cannot hold is refused with a ValueError before any blob exists (_np, _stored): a non-finite parameter, or a folded
+value that is not finite in fp16 (fp32 for biases, the stem and the L2Norm scale). A diverged checkpoint would otherwise lower to inf / NaN
+weights and give NaN detections with no error anywhere.
 """
 import ctypes as C
 from typing import Dict
@@ -43,10 +47,33 @@ class _Blob:
 
 
 def _np(sd, key):
+    """A parameter the lowering reads, as float64. A non-finite entry is refused here: it would reach every output of its layer."""
     v = sd[key]
     if hasattr(v, "detach"):
         v = v.detach().cpu().numpy()
-    return np.asarray(v, dtype=np.float64)
+    a = np.asarray(v, dtype=np.float64)
+    bad = ~np.isfinite(a)
+    if bad.any():
+        idx = tuple(int(i) for i in np.argwhere(bad)[0])
+        raise ValueError(f"non-finite parameter: state_dict['{key}'] is {a[idx]} at output channel {idx[0] if idx else 0} (index {idx}; "
+                         f"{int(bad.sum())} of {a.size} entries are not finite). The checkpoint cannot be lowered.")
+    return a
+
+
+def _stored(a, dtype, key, what):
+    """float64 [output channel, ...] -> the stored format (fp16 weights; fp32 biases, stem weights and the L2Norm scale). A value that
+    does not survive the cast as a finite number is refused, not rescaled: no kernel outside the stem carries a per-channel scale, and a
+    rescale would move the rounding points. Values that round to a subnormal or to zero pass."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        out = a.astype(dtype)
+    bad = ~np.isfinite(out)
+    if bad.any():
+        idx = tuple(int(i) for i in np.argwhere(bad)[0])
+        name = {np.float16: "fp16", np.float32: "fp32"}[dtype]
+        raise ValueError(f"folded value out of range: {what} of state_dict['{key}'] is {a[idx]} at output channel {idx[0]} (index {idx}; "
+                         f"{int(bad.sum())} of {a.size} entries), which {name} (largest finite value {float(np.finfo(dtype).max):g}) "
+                         f"cannot hold. The checkpoint cannot be lowered.")
+    return out
 
 
 def _fold(sd, node, cout):
@@ -57,9 +84,14 @@ def _fold(sd, node, cout):
         beta = _np(sd, node.bn_key + ".bias")
         mu = _np(sd, node.bn_key + ".running_mean")
         var = _np(sd, node.bn_key + ".running_var")
-        s = g / np.sqrt(var + node.bn_eps)
-        return s, (b - mu) * s + beta
+        with np.errstate(all="ignore"):                       # (a zero or negative var + eps: the result is refused by _stored)
+            s = g / np.sqrt(var + node.bn_eps)
+            return s, (b - mu) * s + beta
     return np.ones(cout), b
+
+
+def _what(node, part):
+    return f"the {part} folded with BatchNorm '{node.bn_key}'" if node.bn_key else f"the {part}"
 
 
 class LoweredModel:
@@ -73,6 +105,7 @@ class LoweredModel:
         for i, t in enumerate(g.tensors):
             self.tensors[i] = _lib.TensorDesc(t.c, t.h, t.w, _lib.DN_T[t.kind])
         ops = []
+        bias_key = lambda nd: (nd.conv_key if nd.has_bias else nd.bn_key) + ".bias"    # the parameter a refused bias is reported under
         head_inputs = {nd.inp for nd in g.nodes if nd.head}          # tensors a head op reads: the depthwise outputs of the SSDLite heads
         for nd in g.nodes:
             o = _lib.OpDesc()
@@ -84,15 +117,19 @@ class LoweredModel:
             if nd.op == "stem":
                 w = _np(state_dict, nd.conv_key + ".weight")              # [cout, 3, k, k]
                 s, b = _fold(state_dict, nd, nd.cout)
-                w = w * s[:, None, None, None]
-                o.w_off = blob.add(w.transpose(1, 2, 3, 0).reshape(-1, nd.cout).astype(np.float32))
-                o.b_off = blob.add(b.astype(np.float32))
+                with np.errstate(all="ignore"):
+                    w = w * s[:, None, None, None]
+                w = _stored(w, np.float32, nd.conv_key + ".weight", _what(nd, "stem weight"))
+                o.w_off = blob.add(w.transpose(1, 2, 3, 0).reshape(-1, nd.cout))
+                o.b_off = blob.add(_stored(b, np.float32, bias_key(nd), _what(nd, "bias")))
             elif nd.op == "pw":
                 w = _np(state_dict, nd.conv_key + ".weight").reshape(nd.cout, nd.cin)
                 s, b = _fold(state_dict, nd, nd.cout)
-                wf = (w * s[:, None]).astype(np.float16)
+                with np.errstate(all="ignore"):
+                    w = w * s[:, None]
+                wf = _stored(w, np.float16, nd.conv_key + ".weight", _what(nd, "1x1 weight"))
                 o.w_off = blob.add(wf)
-                o.b_off = blob.add(b.astype(np.float32))
+                o.b_off = blob.add(_stored(b, np.float32, bias_key(nd), _what(nd, "bias")))
                 if nd.cin % 8 == 0:
                     # second copy in MFMA-fragment order for the kernels that stream weights straight from L2 into A fragments
                     # (tail.hip, the strip kernel, headfuse.hip -- class AND box heads): [cout tile of 32][16-deep K step][lane = (k half, channel)][8 halfs]
@@ -101,9 +138,11 @@ class LoweredModel:
             elif nd.op == "dw":
                 w = _np(state_dict, nd.conv_key + ".weight").reshape(nd.cin, nd.k * nd.k)
                 s, b = _fold(state_dict, nd, nd.cin)
-                wf = (w * s[:, None]).astype(np.float16)                   # [c][k*k]
+                with np.errstate(all="ignore"):
+                    w = w * s[:, None]
+                wf = _stored(w, np.float16, nd.conv_key + ".weight", _what(nd, "depthwise weight"))   # [c][k*k]
                 o.w_off = blob.add(np.ascontiguousarray(wf.T))             # [k*k][c]
-                o.b_off = blob.add(b.astype(np.float32))
+                o.b_off = blob.add(_stored(b, np.float32, bias_key(nd), _what(nd, "bias")))
                 if nd.out in head_inputs and nd.k == 3 and nd.cin % 8 == 0:
                     # second copy in GROUP-major order for the fused head launch (headfuse.hip): [c / 8][9 taps][8] -- the nine taps of an
                     # 8-channel group are 144 contiguous bytes (three scalar loads / one piece of an LDS-DMA instead of nine strided rows)
@@ -111,20 +150,23 @@ class LoweredModel:
             elif nd.op == "se":
                 w1 = _np(state_dict, nd.fc1_key + ".weight").reshape(nd.squeeze, nd.cin)
                 w2 = _np(state_dict, nd.fc2_key + ".weight").reshape(nd.cin, nd.squeeze)
-                o.w_off = blob.add(np.ascontiguousarray(w1.T).astype(np.float16))   # fc1 transposed: [c][squeeze] fp16
-                o.b_off = blob.add(_np(state_dict, nd.fc1_key + ".bias").astype(np.float32))
-                o.w2_off = blob.add(np.ascontiguousarray(w2.T).astype(np.float16))  # fc2 transposed: [squeeze][c] fp16
-                o.b2_off = blob.add(_np(state_dict, nd.fc2_key + ".bias").astype(np.float32))
+                w1 = _stored(w1, np.float16, nd.fc1_key + ".weight", "the SE fc1 weight")
+                w2 = _stored(w2, np.float16, nd.fc2_key + ".weight", "the SE fc2 weight")
+                o.w_off = blob.add(np.ascontiguousarray(w1.T))                      # fc1 transposed: [c][squeeze] fp16
+                o.b_off = blob.add(_stored(_np(state_dict, nd.fc1_key + ".bias"), np.float32, nd.fc1_key + ".bias", "the SE fc1 bias"))
+                o.w2_off = blob.add(np.ascontiguousarray(w2.T))                     # fc2 transposed: [squeeze][c] fp16
+                o.b2_off = blob.add(_stored(_np(state_dict, nd.fc2_key + ".bias"), np.float32, nd.fc2_key + ".bias", "the SE fc2 bias"))
                 o.pool_pixels = nd.stride
                 o.stride = 1
             elif nd.op == "conv":
                 w = _np(state_dict, nd.conv_key + ".weight")               # [cout, cin, k, k]
                 s, b = _fold(state_dict, nd, nd.cout)
-                w = (w * s[:, None, None, None]).transpose(0, 2, 3, 1).reshape(nd.cout, -1)   # [cout][ky][kx][cin]
-                o.w_off = blob.add(w.astype(np.float16))
-                o.b_off = blob.add(b.astype(np.float32))
+                with np.errstate(all="ignore"):
+                    w = (w * s[:, None, None, None]).transpose(0, 2, 3, 1).reshape(nd.cout, -1)   # [cout][ky][kx][cin]
+                o.w_off = blob.add(_stored(w, np.float16, nd.conv_key + ".weight", _what(nd, "conv weight")))
+                o.b_off = blob.add(_stored(b, np.float32, bias_key(nd), _what(nd, "bias")))
             elif nd.op == "l2norm":
-                o.w_off = blob.add(_np(state_dict, nd.scale_key).astype(np.float32))
+                o.w_off = blob.add(_stored(_np(state_dict, nd.scale_key), np.float32, nd.scale_key, "the L2Norm scale"))
             elif nd.op == "maxpool":
                 pass
             else:

@@ -64,8 +64,13 @@ class _Env:
                 os.environ[k] = v
 
 
-def _model(name, ncls, size, dev):
-    return models.load_synthetic(getattr(models, name)(num_classes=ncls, **({"image_size": size} if size else {})), 0).to(dev)
+def _model(name, ncls, size, dev, weights=None):
+    """weights: None for the synthetic weights, or a regime of tests/trained_like.py"""
+    m = getattr(models, name)(num_classes=ncls, **({"image_size": size} if size else {}))
+    if weights is not None:
+        import trained_like
+        return trained_like.load(m, weights).to(dev)
+    return models.load_synthetic(m, 0).to(dev)
 
 
 def _labels(m, imgs, dev):
@@ -115,8 +120,8 @@ def _check(what, label, got, y, e, fp16, stats, fails, layout="nchw"):
 _CACHE = {}
 
 
-def _run(cfg):
-    key = _cid(cfg)
+def _run(cfg, weights=None):
+    key = _cid(cfg) + (f"-{weights}" if weights else "")
     if key in _CACHE:
         return _CACHE[key]
     name, ncls, n, env, size = cfg
@@ -124,7 +129,7 @@ def _run(cfg):
     L = _lib.lib()
     t0 = time.time()
     with _Env(env):
-        lab_m = _model(name, ncls, size, dev)
+        lab_m = _model(name, ncls, size, dev, weights)
         g = lab_m.graph
         W, H = g.size
         imgs = torch.from_numpy(synth.images(11, n, H, W))
@@ -134,7 +139,7 @@ def _run(cfg):
         torch.cuda.synchronize()
         lab_m.release()
         with _Env({"DN_WS_REUSE": "0"}):
-            m = _model(name, ncls, size, dev)
+            m = _model(name, ncls, size, dev, weights)
             h = C.c_void_p(m._plan(dev))
             b = m._buffers_for(n, H, W, dev)
             ws = b["ws"]

@@ -35,9 +35,13 @@ def _golden(golden_dir, name):
     return np.load(p)
 
 
-def _model(name, z=None, **kw):
+def _model(name, z=None, weights=None, **kw):
+    """weights: None for the synthetic weights (demonet_amd/synth.py), or a regime of tests/trained_like.py"""
     ncls = int(z["num_classes"]) if z is not None else kw.pop("num_classes", 91)
     m = getattr(models, name)(num_classes=ncls, **kw)
+    if weights is not None:
+        import trained_like
+        return trained_like.load(m, weights).cuda()
     models.load_synthetic(m, int(z["weight_seed"]) if z is not None else 0)
     return m.cuda()
 
@@ -682,7 +686,9 @@ def test_head_group_fast_k_loop_bit_identical(n, monkeypatch):
 
 @pytest.mark.parametrize("name,ncls,kw,n", [("ssdlite320_mobilenet_v3_large", 91, {}, 64), ("ssdlite320_mobilenet_v3_large", 91, {}, 37),
                                            ("ssdlite320_mobilenet_v3_large", 91, {}, 3), ("ssdlite320_mobilenet_v3_large", 21, {}, 9),
-                                           ("ssd_lite_mobilenet_v2", 91, {}, 16), ("ssd_lite_mobilenet_v2", 21, {"image_size": 300}, 9)])
+                                           ("ssd_lite_mobilenet_v2", 91, {}, 16), ("ssd_lite_mobilenet_v2", 21, {"image_size": 300}, 9),
+                                           # trained-like weights with scaled head outputs: logit gaps far past 40, regressions past the clip
+                                           ("ssdlite320_mobilenet_v3_large", 91, {"weights": "hot_heads"}, 5)])
 def test_fused_head_launch_is_bit_identical(name, ncls, kw, n, monkeypatch):
     """Round 4 (headfuse.hip, default on): the heads of every pyramid level -- depthwise 3x3 + ReLU6 and the 1x1 behind it, class and box head -- run as ONE
     launch with the depthwise computed inside the GEMM's operand staging (`_prediction_block`, ssd_mobilenetv3.py:27-36; generalized_ssd.py:60-74).
@@ -1095,7 +1101,9 @@ def test_vgg_without_workspace_reuse(name, n, size, monkeypatch):
                                                ("ssdlite320_mobilenet_v3_large", 91, 5, {"score_thresh": 0.05, "detections_per_img": 100, "topk_candidates": 200}),
                                                ("ssdlite320_mobilenet_v3_large", 91, 8, {"score_thresh": 1e-6}),
                                                ("ssd_lite_mobilenet_v2", 21, 40, {"image_size": 300}), ("ssd_lite_mobilenet_v2", 91, 5, {})]
-                         + [("ssd_lite_mobilenet_v2", 21, 5, {"image_size": s}) for s in (160, 192, 301, 496, 512)])
+                         + [("ssd_lite_mobilenet_v2", 21, 5, {"image_size": s}) for s in (160, 192, 301, 496, 512)]
+                         # trained-like weights with scaled head outputs: pp_exp_nonpos past its cut, dw / dh past the clamp in both launches
+                         + [("ssdlite320_mobilenet_v3_large", 91, 37, {"weights": "hot_heads"})])
 def test_softmax_and_decode_in_the_head_launch_are_bit_identical(name, ncls, n, post, monkeypatch):
     """Round 5 (headfuse.hip SM = true, DN_HEAD_SOFTMAX default 1): softmax over the classes, decode_single + clip and the score-histogram rows
     (generalized_ssd.py:354,362-363; _utils.py:187-224) run in the epilogue of the fused head launch -- the logits never reach memory and
