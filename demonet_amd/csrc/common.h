@@ -72,6 +72,7 @@ __device__ __forceinline__ void fma_mix_h8(float (&acc)[8], const uint4& e, cons
 }
 
 static inline int dn_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }      // workspace carving: every array starts on a 256-byte boundary
 
 // Environment knob, read on EVERY call -- never latched in a static -- so that a test can A/B two settings in one process
 // (a new plan / the next eager launch sees the new value; a captured hipGraph keeps what it was captured with).

@@ -1,42 +1,31 @@
 // Weighted boxes fusion: dn_fuse_detections, the reducer for sources that are different opinions about the same objects -- the plain
 // and the flipped pass of one image, several checkpoints. Where dn_merge_detections (sliced.hip) keeps the best box of an overlapping set, this
 // averages the set with the scores as weights and marks down what only some of the sources saw (Solovyev, Wang, Gabruseva 2019; conf_type 'avg').
-//   1 - 3  fuse_keys / fuse_rank / fuse_scatter   the ranking of the candidates by v = score * weight: the merge's key / rank-by-counting / scatter
-//                                                 pattern, restated here so that sliced.hip stays as it is
+//   1      fuse_keys_kernel                       v = score * weight of every candidate as a key
+//   2 - 3  detset_rank (detset.hip)               the ranking of the candidates: rank by counting and scatter, the merge's own
 //   4      fuse_walk_kernel                       one wave per group walks the ranking and builds the cluster table
-//   5      fuse_rank_kernel once more             ranks the clusters by their final score (the table's keys take the place of the candidates')
+//   5      detset_rank once more, no scatter      ranks the clusters by their final score (the table's keys take the place of the candidates')
 //   6      fuse_emit_kernel                       cluster of rank r -> output row r; the rows behind the count are cleared
-// Compiled with -ffp-contract=off: every operation of the header's text rounds once, as tests/wbf_ref.py restates it. No inline asm, no float
-// atomics; the only atomics are unsigned additions of partial counts, whose sum does not depend on their order.
-#include "common.h"
+// Compiled with -ffp-contract=off: every operation of the header's text rounds once, as tests/wbf_ref.py restates it. No inline asm, no atomics
+// in this file.
+#include "detset.h"
 
 namespace {
 
-size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 constexpr int FZ_MAX_D = 512, FZ_MAX_SLOTS = 8192;
-constexpr int FZ_NT = 256;                 // threads of the ranking and emit workgroups
-constexpr int FZ_OTHERS = 2048;            // keys one rank workgroup compares its 256 keys with
-constexpr int FZ_GROUPS = 64;              // groups per launch: their source ranges travel as a kernel argument
+constexpr int FZ_NT = 256;                 // threads of the keys and emit workgroups
 constexpr int FZ_WAVE = 64;                // the walk's workgroup: one wave
 constexpr int FZ_SCAN = 4, FZ_SCAN_WS = 8;  // clusters a lane examines per step of its scan: in LDS, in the workspace
 constexpr int FZ_LDS_CLUSTERS = 1024;      // clusters the walk keeps in LDS, 48 bytes each (a multiple of 64 * FZ_SCAN); the others live in the workspace
 static_assert(FZ_LDS_CLUSTERS % (FZ_WAVE * FZ_SCAN) == 0, "a scan step must stay inside the LDS table");
-constexpr unsigned FZ_END = 0xFFFFFFFFu;   // order[]: no candidate of this rank
 constexpr int FZ_NONE = 0x7FFFFFFF;        // no cluster matched
-
-struct GroupTab {
-    int count;
-    int begin[FZ_GROUPS + 1];      // sources begin[g] .. begin[g + 1] - 1 form group g of this launch
-    int first;                     // index of group 0 of this launch among the call's groups
-};
 
 // One entry per slot; cluster c of a group lives at the group's first slot + c (a group has at most as many clusters as candidates).
 struct FuseBuffers {
     unsigned* keys;        // [N] launches 1 - 3: v as an unsigned that orders like the float, 0: not a candidate. From the walk on: the same for the
                            //     cluster's final score, 0: no cluster
     unsigned* rank;        // [N] candidates (later: clusters) of the same group that rank higher
-    unsigned* order;       // [N] flattened index of the candidate of each rank, per group from the group's first slot; FZ_END behind the last
+    unsigned* order;       // [N] flattened index of the candidate of each rank, per group from the group's first slot; DS_END behind the last
     float4* fbox;          // [N] fused box
     float4* acc;           // [N] A_k = sum of v * coord_k (used by the clusters beyond the walk's LDS table only)
     long long* label;      // [N]
@@ -59,15 +48,8 @@ FuseBuffers fuse_buffers(void* ws, size_t n_slots) {
     return b;
 }
 
-// a float as an unsigned with the order of the floats (-0 counts as +0), never 0; a NaN ranks behind every number (-inf maps to 0x007FFFFF)
-__device__ __forceinline__ unsigned fz_key(const float f) {
-    if (f != f) return 1u;
-    const unsigned u = f == 0.f ? 0u : __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // Launch 1, one thread per slot (source s, row j; flattened index i = s * d + j): v = score * weight[s]; a candidate (j < counts[s], v not NaN,
-// v >= skip_thresh, v > 0) gets v's key, every other slot 0. Also clears what the next two launches fill.
+// v >= skip_thresh, v > 0) gets v's dn_order_key, every other slot 0. Also clears what the two ranking launches fill.
 __global__ __launch_bounds__(FZ_NT) void fuse_keys_kernel(const float* __restrict__ scores, const int32_t* __restrict__ counts,
                                                           const float* __restrict__ weights, float skip_thresh, int n_slots, int d,
                                                           unsigned* __restrict__ keys, unsigned* __restrict__ rank, unsigned* __restrict__ order) {
@@ -75,69 +57,9 @@ __global__ __launch_bounds__(FZ_NT) void fuse_keys_kernel(const float* __restric
     if (i >= n_slots) return;
     const int s = i / d, j = i - s * d;
     const float v = scores[i] * (weights ? weights[s] : 1.0f);
-    keys[i] = (j < counts[s] && v == v && v >= skip_thresh && v > 0.f) ? fz_key(v) : 0u;
+    keys[i] = (j < counts[s] && v == v && v >= skip_thresh && v > 0.f) ? dn_order_key(v) : 0u;
     rank[i] = 0u;
-    order[i] = FZ_END;
-}
-
-// Launches 2 and 5, rank by counting: grid (blocks of 256 own keys, chunks of FZ_OTHERS other keys, groups). The rank of a key is the number of
-// keys of its group that are larger, or equal with a smaller index. Both ranges are aligned to 256, so a 256-key piece of the chunk lies entirely
-// below the own keys (equal counts), entirely above (equal does not count) or is the own block itself. The partial counts of the chunks meet in
-// rank[] by unsigned atomic addition: the sum is the same in any order.
-__global__ __launch_bounds__(FZ_NT) void fuse_rank_kernel(const unsigned* __restrict__ keys, unsigned* __restrict__ rank, int d, GroupTab gt) {
-    __shared__ unsigned tile[FZ_OTHERS];
-    const int g = blockIdx.z;
-    const int base = gt.begin[g] * d, n = (gt.begin[g + 1] - gt.begin[g]) * d;
-    const int i0 = blockIdx.x * FZ_NT, j0 = blockIdx.y * FZ_OTHERS;
-    if (i0 >= n || j0 >= n) return;
-    const int tid = threadIdx.x, i = i0 + tid;
-    const unsigned mine = i < n ? keys[base + i] : 0u;
-    if (!__syncthreads_or(mine != 0u)) return;
-#pragma unroll
-    for (int u = 0; u < FZ_OTHERS / FZ_NT; ++u) {
-        const int j = j0 + u * FZ_NT + tid;
-        tile[u * FZ_NT + tid] = j < n ? keys[base + j] : 0u;
-    }
-    __syncthreads();
-    unsigned cnt = 0u;
-    for (int u = 0; u < FZ_OTHERS / FZ_NT; ++u) {
-        const int js = j0 + u * FZ_NT;
-        if (js >= n) break;
-        const uint4* t4 = reinterpret_cast<const uint4*>(&tile[u * FZ_NT]);
-        if (js < i0) {
-#pragma unroll 8
-            for (int q = 0; q < FZ_NT / 4; ++q) {
-                const uint4 o = t4[q];
-                cnt += (o.x >= mine) + (o.y >= mine) + (o.z >= mine) + (o.w >= mine);
-            }
-        } else if (js > i0) {
-#pragma unroll 8
-            for (int q = 0; q < FZ_NT / 4; ++q) {
-                const uint4 o = t4[q];
-                cnt += (o.x > mine) + (o.y > mine) + (o.z > mine) + (o.w > mine);
-            }
-        } else {
-#pragma unroll 8
-            for (int q = 0; q < FZ_NT / 4; ++q) {
-                const uint4 o = t4[q];
-                const int jq = 4 * q;
-                cnt += (o.x > mine || (o.x == mine && jq + 0 < tid)) + (o.y > mine || (o.y == mine && jq + 1 < tid)) +
-                       (o.z > mine || (o.z == mine && jq + 2 < tid)) + (o.w > mine || (o.w == mine && jq + 3 < tid));
-            }
-        }
-    }
-    if (mine != 0u) atomicAdd(&rank[base + i], cnt);
-}
-
-// Launch 3: order[first slot of the group + rank] = flattened index. Ranks of a group's candidates are 0 .. candidates - 1, each once.
-__global__ __launch_bounds__(FZ_NT) void fuse_scatter_kernel(const unsigned* __restrict__ keys, const unsigned* __restrict__ rank,
-                                                             unsigned* __restrict__ order, int d, GroupTab gt) {
-    const int g = blockIdx.y;
-    const int base = gt.begin[g] * d, n = (gt.begin[g + 1] - gt.begin[g]) * d;
-    const int i = blockIdx.x * FZ_NT + threadIdx.x;
-    if (i >= n || keys[base + i] == 0u) return;
-    const unsigned r = rank[base + i];
-    if (r < (unsigned)n) order[base + r] = (unsigned)(base + i);
+    order[i] = DS_END;
 }
 
 struct FuseArgs {
@@ -148,15 +70,11 @@ struct FuseArgs {
     float4* boxes_out; float* scores_out; int64_t* labels_out; int32_t* counts_out; int32_t* members_out;
 };
 
-// IoU of the cluster's fused box f with the candidate b (area ab): fp32, the operation order of the merge (DN_MERGE_IOU). thresh >= 0, so a pair
-// without intersection (overlap 0 or NaN) cannot pass `> thresh`: -1 stands for "no match" there, as it does for a NaN overlap at the caller.
+// IoU of the cluster's fused box f with the candidate b (area ab): the merge's (DN_MERGE_IOU) by construction, both divide dn_box_inter by the same
+// sum. thresh >= 0, so a pair without intersection (overlap 0 or NaN) cannot pass `> thresh`: -1 stands for "no match" there, as it does for a NaN
+// overlap at the caller.
 __device__ __forceinline__ float fz_iou(const float4 f, const float4 b, const float ab) {
-    const float xx1 = f.x > b.x ? f.x : b.x, yy1 = f.y > b.y ? f.y : b.y;
-    const float xx2 = f.z < b.z ? f.z : b.z, yy2 = f.w < b.w ? f.w : b.w;
-    float w = xx2 - xx1, h = yy2 - yy1;
-    if (w < 0.0f) w = 0.0f;
-    if (h < 0.0f) h = 0.0f;
-    const float inter = w * h;
+    const float inter = dn_box_inter(f, b);
     if (inter == 0.0f) return -1.0f;
     const float af = (f.z - f.x) * (f.w - f.y);
     return inter / (af + ab - inter);
@@ -210,8 +128,8 @@ __global__ __launch_bounds__(FZ_WAVE) void fuse_walk_kernel(FuseArgs a, GroupTab
 
     // the candidate of rank pos + lane: false when the ranking has ended there
     auto fetch = [&](const int pos, float4& b, float& v, long long& lb) -> bool {
-        const unsigned idx = pos + lane < n ? a.b.order[base + pos + lane] : FZ_END;
-        if (idx == FZ_END) return false;
+        const unsigned idx = pos + lane < n ? a.b.order[base + pos + lane] : DS_END;
+        if (idx == DS_END) return false;
         const unsigned s = idx / (unsigned)a.d;
         const float2 o = a.offsets[s];
         b = a.boxes[idx];
@@ -337,7 +255,7 @@ __global__ __launch_bounds__(FZ_WAVE) void fuse_walk_kernel(FuseArgs a, GroupTab
             const float t = (float)T;
             const float sc = ((s / t) * (W < t ? W : t)) / W;
             sv[c] = sc;
-            k = fz_key(sc);
+            k = dn_order_key(sc);      // (a NaN score ranks behind every number)
         }
         a.b.keys[base + c] = k;
         a.b.rank[base + c] = 0u;
@@ -370,13 +288,6 @@ __global__ __launch_bounds__(FZ_NT) void fuse_emit_kernel(FuseArgs a, GroupTab g
     }
 }
 
-bool fuse_sizes_ok(int s_total, int d, int groups) { return s_total >= 1 && d >= 1 && groups >= 1; }
-bool fuse_groups_ok(const int32_t* group_begin, int groups, int s_total) {
-    if (group_begin[0] < 0 || group_begin[groups] > s_total) return false;
-    for (int g = 0; g < groups; ++g)
-        if (group_begin[g] > group_begin[g + 1]) return false;
-    return true;
-}
 bool fuse_supported(int s_total, int d, const int32_t* group_begin, int groups) {
     if (d > FZ_MAX_D || (long long)s_total * d > 0x7FFFFFFFll) return false;
     for (int g = 0; g < groups; ++g)
@@ -388,7 +299,7 @@ bool fuse_supported(int s_total, int d, const int32_t* group_begin, int groups) 
 
 extern "C" __attribute__((visibility("default"))) size_t dn_fuse_detections_workspace_bytes(int s_total, int d, const int32_t* group_begin,
                                                                                            int groups) {
-    if (!group_begin || !fuse_sizes_ok(s_total, d, groups) || !fuse_groups_ok(group_begin, groups, s_total) ||
+    if (!group_begin || !detset_sizes_ok(s_total, d, groups) || !detset_groups_ok(group_begin, groups, s_total) ||
         !fuse_supported(s_total, d, group_begin, groups))
         return 0;
     return fuse_buffers(nullptr, (size_t)s_total * d).bytes;
@@ -400,17 +311,11 @@ extern "C" __attribute__((visibility("default"))) int dn_fuse_detections(const f
                                                                         float skip_thresh, int d_out, float* boxes_out, float* scores_out,
                                                                         int64_t* labels_out, int32_t* counts_out, int32_t* members_out,
                                                                         void* workspace, size_t workspace_bytes, void* stream) {
-    DN_REQUIRE(boxes && scores && labels && counts && offsets && group_begin && boxes_out && scores_out && labels_out && counts_out && workspace,
-               "dn_fuse_detections: null argument");
-    DN_REQUIRE(fuse_sizes_ok(s_total, d, groups) && d_out >= 1, "dn_fuse_detections: bad sizes s_total=%d d=%d groups=%d d_out=%d", s_total, d, groups,
-               d_out);
+    if (const int rc = detset_check("dn_fuse_detections", boxes, scores, labels, counts, offsets, s_total, d, group_begin, groups, d_out, boxes_out,
+                                    scores_out, labels_out, counts_out, workspace))
+        return rc;
     DN_REQUIRE(thresh >= 0.f && skip_thresh >= 0.f, "dn_fuse_detections: thresh=%g and skip_thresh=%g must be numbers >= 0", (double)thresh,
                (double)skip_thresh);
-    DN_REQUIRE(((reinterpret_cast<size_t>(boxes) | reinterpret_cast<size_t>(boxes_out) | reinterpret_cast<size_t>(workspace)) & 15) == 0 &&
-                   ((reinterpret_cast<size_t>(offsets) | reinterpret_cast<size_t>(labels) | reinterpret_cast<size_t>(labels_out)) & 7) == 0,
-               "dn_fuse_detections: boxes, boxes_out and the workspace must be 16-byte aligned, offsets and labels 8-byte aligned");
-    DN_REQUIRE(fuse_groups_ok(group_begin, groups, s_total), "dn_fuse_detections: group_begin must not decrease and must stay in 0 .. s_total=%d",
-               s_total);
     if (d_out > FZ_MAX_D || !fuse_supported(s_total, d, group_begin, groups)) {
         dn_set_error("dn_fuse_detections: d=%d and d_out=%d at most %d, at most %d slots (sources * d) per group, s_total * d below 2^31", d, d_out,
                      FZ_MAX_D, FZ_MAX_SLOTS);
@@ -432,26 +337,13 @@ extern "C" __attribute__((visibility("default"))) int dn_fuse_detections(const f
     dn_note_kernel("fuse_keys_kernel");
     hipLaunchKernelGGL(fuse_keys_kernel, dim3(dn_cdiv((long)n_slots, FZ_NT)), dim3(FZ_NT), 0, s, scores, counts, weights, skip_thresh, (int)n_slots, d,
                        a.b.keys, a.b.rank, a.b.order);
-    for (int g0 = 0; g0 < groups; g0 += FZ_GROUPS) {
+    for (int g0 = 0; g0 < groups; g0 += DS_GROUPS) {
         GroupTab gt;
-        gt.count = groups - g0 < FZ_GROUPS ? groups - g0 : FZ_GROUPS;
-        gt.first = g0;
-        int slots = 0;
-        for (int g = 0; g <= FZ_GROUPS; ++g) gt.begin[g] = group_begin[g0 + (g < gt.count ? g : gt.count)];
-        for (int g = 0; g < gt.count; ++g) slots = (gt.begin[g + 1] - gt.begin[g]) * d > slots ? (gt.begin[g + 1] - gt.begin[g]) * d : slots;
-        const dim3 rank_grid(dn_cdiv(slots, FZ_NT), dn_cdiv(slots, FZ_OTHERS), gt.count);
-        if (slots > 0) {
-            dn_note_kernel("fuse_rank_kernel");
-            hipLaunchKernelGGL(fuse_rank_kernel, rank_grid, dim3(FZ_NT), 0, s, a.b.keys, a.b.rank, d, gt);
-            dn_note_kernel("fuse_scatter_kernel");
-            hipLaunchKernelGGL(fuse_scatter_kernel, dim3(dn_cdiv(slots, FZ_NT), gt.count), dim3(FZ_NT), 0, s, a.b.keys, a.b.rank, a.b.order, d, gt);
-        }
+        const int slots = detset_chunk(group_begin, groups, g0, d, gt);
+        detset_rank(a.b.keys, a.b.rank, a.b.order, d, gt, slots, s);
         dn_note_kernel("fuse_walk_kernel");
         hipLaunchKernelGGL(fuse_walk_kernel, dim3(gt.count), dim3(FZ_WAVE), 0, s, a, gt);
-        if (slots > 0) {
-            dn_note_kernel("fuse_rank_kernel");
-            hipLaunchKernelGGL(fuse_rank_kernel, rank_grid, dim3(FZ_NT), 0, s, a.b.keys, a.b.rank, d, gt);
-        }
+        detset_rank(a.b.keys, a.b.rank, nullptr, d, gt, slots, s);      // the clusters, by the keys the walk has left
         dn_note_kernel("fuse_emit_kernel");
         hipLaunchKernelGGL(fuse_emit_kernel, dim3(dn_cdiv(slots > d_out ? slots : d_out, FZ_NT), gt.count), dim3(FZ_NT), 0, s, a, gt);
     }

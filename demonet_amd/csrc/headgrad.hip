@@ -35,8 +35,6 @@ constexpr int HG_MAXBLK = 128;       // workgroups (= partial maxima) of hg_max_
 constexpr int HG_LD = 40;            // LDS row stride in halfs of a [64][32] operand tile: 80 bytes keeps the 16-byte fragment reads aligned
 constexpr int HG_MAX_SPLIT = 16;
 
-inline size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct HgShape {
     int n, h, w, c, cout, hw, P;
     long dy_img_stride;

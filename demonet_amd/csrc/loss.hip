@@ -381,8 +381,6 @@ __global__ __launch_bounds__(256) void ssd_loss_backward_kernel(const float* __r
     }
 }
 
-size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // dn_ssd_loss_train's state, in order: matched [n][A] int64, weight [n][A] uint8, select [n][4] uint32, normaliser fp32
 struct LossState {
     long long* matched;

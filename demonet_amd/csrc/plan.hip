@@ -38,8 +38,6 @@ void dn_set_error(const char* fmt, ...) {
 extern "C" const char* dn_last_error(void) { return g_err; }
 extern "C" int dn_abi_version(void) { return DN_ABI_VERSION; }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int dn_knob(const char* name, int dflt) {
     const char* v = getenv(name);
     return v ? atoi(v) : dflt;
@@ -234,7 +232,7 @@ static const Layout& get_layout(dn_plan* p, int n) {
     }
     if (!p->ws_reuse) {
         for (size_t i = 0; i < T; ++i)
-            if (L.tbytes[i]) { L.toff[i] = off; off += align256(L.tbytes[i]); }
+            if (L.tbytes[i]) { L.toff[i] = off; off += a256(L.tbytes[i]); }
     } else {
         // Liveness reuse: a tensor occupies its block from the launch that writes it to the last launch that reads it (launch
         // time = op index, with the ops of one fused / grouped launch sharing a time step); blocks are placed first-fit at the
@@ -279,7 +277,7 @@ static const Layout& get_layout(dn_plan* p, int n) {
             if (L.tbytes[i] && !inner[i] && born[i] >= 0) order.push_back(i);
         std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return born[a] < born[b]; });
         for (size_t i : order) {
-            const size_t need = align256(L.tbytes[i]);
+            const size_t need = a256(L.tbytes[i]);
             std::vector<std::pair<size_t, size_t>> busy;       // blocks alive at some point of [born, dies]
             for (const Blk& b : placed)
                 if (!(b.dies < born[i] || b.born > dies[i])) busy.push_back({b.off, b.off + b.bytes});
@@ -293,26 +291,26 @@ static const Layout& get_layout(dn_plan* p, int n) {
             placed.push_back({at, need, born[i], dies[i]});
             off = std::max(off, at + need);
         }
-        L.arena = align256(off);
+        L.arena = a256(off);
         off = L.arena * (size_t)S_chains;
     }
     L.resized_off = off;
-    off += align256((size_t)n * 3 * p->d.image_h * p->d.image_w * 4);
+    off += a256((size_t)n * 3 * p->d.image_h * p->d.image_w * 4);
     L.logits_off = off;
-    off += align256((size_t)n * p->d.num_anchors * p->d.num_classes * 4);
+    off += a256((size_t)n * p->d.num_anchors * p->d.num_classes * 4);
     L.reg_off = off;
-    off += align256((size_t)n * p->d.num_anchors * 4 * 4);
+    off += a256((size_t)n * p->d.num_anchors * 4 * 4);
     L.scale_off = off;
-    off += align256((size_t)n * 2 * 4);
+    off += a256((size_t)n * 2 * 4);
     L.secnt_off = off;
-    off += align256((size_t)n * p->n_se_in_dw * 4 + 4);
+    off += a256((size_t)n * p->n_se_in_dw * 4 + 4);
     L.post_off = off;
     {
         const int S = batch_split(p, n);          // one private post-process scratch slice per sub-batch branch
-        L.post_bytes = (size_t)S * align256(postprocess_ws_bytes(sub_count(n, S, 0), p->d.num_anchors, p->d.num_classes,
+        L.post_bytes = (size_t)S * a256(postprocess_ws_bytes(sub_count(n, S, 0), p->d.num_anchors, p->d.num_classes,
                                                                  p->d.topk_candidates, p->d.detections_per_img));
     }
-    off += align256(L.post_bytes);
+    off += a256(L.post_bytes);
     L.total = off;
     return p->layouts.emplace(n, std::move(L)).first->second;
 }

@@ -2,15 +2,13 @@
 //   dn_crop_tiles        one gather launch: equal-size tiles of one [3][h][w] image -> [t][3][th][tw], the input of dn_forward
 //   dn_merge_detections  hard NMS over detections that already exist: the outputs of dn_forward for several sources (tiles, the whole image,
 //                        flipped passes, other models), shifted by one offset per source, merged per output image (group)
-// Compiled with -ffp-contract=off: the overlap must round like the formula of oracle/nms_c.c. No inline asm; the only atomics are unsigned
-// additions of partial counts, whose sum does not depend on their order.
+// The merge is keys -> ranking (detset.hip, shared with the box fusion) -> walk. Compiled with -ffp-contract=off: the overlap must round like the
+// formula of oracle/nms_c.c. No inline asm, no atomics in this file.
 #include <vector>
 
-#include "common.h"
+#include "detset.h"
 
 namespace {
-
-size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---------------------------------------------------------------------------------------------------------
 // crop
@@ -64,21 +62,12 @@ __global__ __launch_bounds__(CROP_NT) void crop_tiles_kernel(const float* __rest
 // merge
 // ---------------------------------------------------------------------------------------------------------
 constexpr int MG_MAX_D = 512, MG_MAX_SOURCES = 1024, MG_MAX_SLOTS = 65536;
-constexpr int MG_NT = 256;                 // threads of every merge workgroup; the walk's chunk
-constexpr int MG_OTHERS = 2048;            // keys one rank workgroup compares its 256 keys with
-constexpr int MG_GROUPS = 64;              // groups per launch: their source ranges travel as a kernel argument (no host array is read later)
-constexpr unsigned MG_END = 0xFFFFFFFFu;   // order[]: no candidate of this rank
-
-struct GroupTab {
-    int count;
-    int begin[MG_GROUPS + 1];      // sources begin[g] .. begin[g + 1] - 1 form group g of this launch
-    int first;                     // index of group 0 of this launch among the call's groups
-};
+constexpr int MG_NT = 256;                 // threads of the keys and walk workgroups; the walk's chunk
 
 struct MergeBuffers {
     unsigned* keys;       // [N] score as an unsigned that orders like the float; 0: not a candidate
     unsigned* rank;       // [N] candidates of the same group that rank higher
-    unsigned* order;      // [N] flattened index of the candidate of each rank, per group from the group's first slot; MG_END behind the last
+    unsigned* order;      // [N] flattened index of the candidate of each rank, per group from the group's first slot; DS_END behind the last
     size_t bytes;
 };
 MergeBuffers merge_buffers(void* ws, size_t n_slots) {
@@ -92,8 +81,7 @@ MergeBuffers merge_buffers(void* ws, size_t n_slots) {
 }
 
 // Launch 1, one thread per slot (source s, row j; flattened index i = s * d + j): the key of a candidate (j < counts[s], score not NaN) is its
-// score mapped to an unsigned with the order of the floats (-0 counts as +0: the two compare equal), which is never 0; every other slot gets 0.
-// Also clears what the next two launches fill.
+// score's dn_order_key, which is never 0; every other slot gets 0. Also clears what the two ranking launches (detset.hip) fill.
 __global__ __launch_bounds__(MG_NT) void merge_keys_kernel(const float* __restrict__ scores, const int32_t* __restrict__ counts, int n_slots, int d,
                                                            unsigned* __restrict__ keys, unsigned* __restrict__ rank, unsigned* __restrict__ order) {
     const int i = blockIdx.x * MG_NT + threadIdx.x;
@@ -101,73 +89,10 @@ __global__ __launch_bounds__(MG_NT) void merge_keys_kernel(const float* __restri
     const int s = i / d, j = i - s * d;
     const float sc = scores[i];
     unsigned k = 0u;
-    if (j < counts[s] && sc == sc) {
-        const unsigned u = sc == 0.f ? 0u : __float_as_uint(sc);
-        k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
+    if (j < counts[s] && sc == sc) k = dn_order_key(sc);
     keys[i] = k;
     rank[i] = 0u;
-    order[i] = MG_END;
-}
-
-// Launch 2, rank by counting: grid (blocks of 256 own keys, chunks of MG_OTHERS other keys, groups). The rank of a candidate is the number of
-// candidates of its group with a larger key, or with an equal key and a smaller flattened index. Both ranges are aligned to 256, so a 256-key
-// piece of the chunk lies entirely below the own keys (equal counts), entirely above (equal does not count) or is the own block itself. The
-// partial counts of the chunks meet in rank[] by unsigned atomic addition: the sum is the same in any order.
-__global__ __launch_bounds__(MG_NT) void merge_rank_kernel(const unsigned* __restrict__ keys, unsigned* __restrict__ rank, int d, GroupTab gt) {
-    __shared__ unsigned tile[MG_OTHERS];
-    const int g = blockIdx.z;
-    const int base = gt.begin[g] * d, n = (gt.begin[g + 1] - gt.begin[g]) * d;
-    const int i0 = blockIdx.x * MG_NT, j0 = blockIdx.y * MG_OTHERS;
-    if (i0 >= n || j0 >= n) return;
-    const int tid = threadIdx.x, i = i0 + tid;
-    const unsigned mine = i < n ? keys[base + i] : 0u;
-    if (!__syncthreads_or(mine != 0u)) return;
-#pragma unroll
-    for (int u = 0; u < MG_OTHERS / MG_NT; ++u) {
-        const int j = j0 + u * MG_NT + tid;
-        tile[u * MG_NT + tid] = j < n ? keys[base + j] : 0u;
-    }
-    __syncthreads();
-    unsigned cnt = 0u;
-    for (int u = 0; u < MG_OTHERS / MG_NT; ++u) {
-        const int js = j0 + u * MG_NT;
-        if (js >= n) break;
-        const uint4* t4 = reinterpret_cast<const uint4*>(&tile[u * MG_NT]);
-        if (js < i0) {
-#pragma unroll 8
-            for (int q = 0; q < MG_NT / 4; ++q) {
-                const uint4 o = t4[q];
-                cnt += (o.x >= mine) + (o.y >= mine) + (o.z >= mine) + (o.w >= mine);
-            }
-        } else if (js > i0) {
-#pragma unroll 8
-            for (int q = 0; q < MG_NT / 4; ++q) {
-                const uint4 o = t4[q];
-                cnt += (o.x > mine) + (o.y > mine) + (o.z > mine) + (o.w > mine);
-            }
-        } else {
-#pragma unroll 8
-            for (int q = 0; q < MG_NT / 4; ++q) {
-                const uint4 o = t4[q];
-                const int jq = 4 * q;
-                cnt += (o.x > mine || (o.x == mine && jq + 0 < tid)) + (o.y > mine || (o.y == mine && jq + 1 < tid)) +
-                       (o.z > mine || (o.z == mine && jq + 2 < tid)) + (o.w > mine || (o.w == mine && jq + 3 < tid));
-            }
-        }
-    }
-    if (mine != 0u) atomicAdd(&rank[base + i], cnt);
-}
-
-// Launch 3: order[first slot of the group + rank] = flattened index. Ranks of a group's candidates are 0 .. candidates - 1, each once.
-__global__ __launch_bounds__(MG_NT) void merge_scatter_kernel(const unsigned* __restrict__ keys, const unsigned* __restrict__ rank,
-                                                              unsigned* __restrict__ order, int d, GroupTab gt) {
-    const int g = blockIdx.y;
-    const int base = gt.begin[g] * d, n = (gt.begin[g + 1] - gt.begin[g]) * d;
-    const int i = blockIdx.x * MG_NT + threadIdx.x;
-    if (i >= n || keys[base + i] == 0u) return;
-    const unsigned r = rank[base + i];
-    if (r < (unsigned)n) order[base + r] = (unsigned)(base + i);
+    order[i] = DS_END;
 }
 
 struct MergeArgs {
@@ -182,12 +107,7 @@ struct MergeArgs {
 // skip0: thresh >= 0, so a pair without intersection (overlap 0 or NaN) cannot pass `> thresh` and the division is not needed.
 __device__ __forceinline__ bool mg_suppresses(const float4 a, const float aa, const float4 b, const float ab, const int metric, const float thresh,
                                               const bool skip0) {
-    const float xx1 = a.x > b.x ? a.x : b.x, yy1 = a.y > b.y ? a.y : b.y;
-    const float xx2 = a.z < b.z ? a.z : b.z, yy2 = a.w < b.w ? a.w : b.w;
-    float w = xx2 - xx1, h = yy2 - yy1;
-    if (w < 0.0f) w = 0.0f;
-    if (h < 0.0f) h = 0.0f;
-    const float inter = w * h;
+    const float inter = dn_box_inter(a, b);
     if (skip0 && inter == 0.0f) return false;
     const float den = metric == DN_MERGE_IOS ? (aa < ab ? aa : ab) : (aa + ab - inter);
     return inter / den > thresh;
@@ -199,7 +119,7 @@ __device__ __forceinline__ unsigned long long mg_uniform64(const unsigned long l
     return ((unsigned long long)hi << 32) | lo;
 }
 
-// Launch 4, one workgroup per group: the greedy walk down the ranking in chunks of 256 candidates.
+// Launch 4 (2 and 3 are detset_rank), one workgroup per group: the greedy walk down the ranking in chunks of 256 candidates.
 //   1. thread t takes the candidate of rank pos + t and tests it against the kept list (LDS, at most d_out <= 512 boxes);
 //   2. every survivor builds its row of the chunk's 256 x 256-bit matrix "the surviving candidate j < t of this chunk suppresses me";
 //   3. wave 0 resolves the chunk in rank order, 64 candidates at a time: candidates suppressed by the kept ones of the earlier 64s fall away,
@@ -225,8 +145,8 @@ __global__ __launch_bounds__(MG_NT) void merge_walk_kernel(MergeArgs a, GroupTab
     int nk = 0;
     for (int pos = 0; pos < n && nk < d_out; pos += MG_NT) {
         // 1. my candidate
-        const unsigned idx = pos + tid < n ? a.order[base + pos + tid] : MG_END;
-        const bool valid = idx != MG_END;
+        const unsigned idx = pos + tid < n ? a.order[base + pos + tid] : DS_END;
+        const bool valid = idx != DS_END;
         float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
         float sc = 0.f, ar = 0.f;
         long long lb = 0;
@@ -321,8 +241,6 @@ __global__ __launch_bounds__(MG_NT) void merge_walk_kernel(MergeArgs a, GroupTab
     if (tid == 0) a.counts_out[G] = nk;
 }
 
-bool merge_sizes_ok(int s_total, int d, int groups) { return s_total >= 1 && d >= 1 && groups >= 1; }
-
 }  // namespace
 
 extern "C" __attribute__((visibility("default"))) int dn_crop_tiles(const float* image, int h, int w, const int32_t* origins, int t, int th, int tw,
@@ -348,7 +266,7 @@ extern "C" __attribute__((visibility("default"))) int dn_crop_tiles(const float*
 }
 
 extern "C" __attribute__((visibility("default"))) size_t dn_merge_detections_workspace_bytes(int s_total, int d, int groups) {
-    if (!merge_sizes_ok(s_total, d, groups) || d > MG_MAX_D || (long long)s_total * d > 0x7FFFFFFFll) return 0;
+    if (!detset_sizes_ok(s_total, d, groups) || d > MG_MAX_D || (long long)s_total * d > 0x7FFFFFFFll) return 0;
     return merge_buffers(nullptr, (size_t)s_total * d).bytes;
 }
 
@@ -358,21 +276,12 @@ extern "C" __attribute__((visibility("default"))) int dn_merge_detections(const 
                                                                          int class_agnostic, int d_out, float* boxes_out, float* scores_out,
                                                                          int64_t* labels_out, int32_t* counts_out, int32_t* src_out, void* workspace,
                                                                          size_t workspace_bytes, void* stream) {
-    DN_REQUIRE(boxes && scores && labels && counts && offsets && group_begin && boxes_out && scores_out && labels_out && counts_out && workspace,
-               "dn_merge_detections: null argument");
-    DN_REQUIRE(merge_sizes_ok(s_total, d, groups) && d_out >= 1, "dn_merge_detections: bad sizes s_total=%d d=%d groups=%d d_out=%d", s_total, d, groups,
-               d_out);
+    if (const int rc = detset_check("dn_merge_detections", boxes, scores, labels, counts, offsets, s_total, d, group_begin, groups, d_out, boxes_out,
+                                    scores_out, labels_out, counts_out, workspace))
+        return rc;
     DN_REQUIRE(metric == DN_MERGE_IOU || metric == DN_MERGE_IOS, "dn_merge_detections: unknown metric %d", metric);
     DN_REQUIRE(class_agnostic == 0 || class_agnostic == 1, "dn_merge_detections: class_agnostic must be 0 or 1, got %d", class_agnostic);
     DN_REQUIRE(thresh == thresh, "dn_merge_detections: thresh is NaN");
-    DN_REQUIRE(((reinterpret_cast<size_t>(boxes) | reinterpret_cast<size_t>(boxes_out) | reinterpret_cast<size_t>(workspace)) & 15) == 0 &&
-                   ((reinterpret_cast<size_t>(offsets) | reinterpret_cast<size_t>(labels) | reinterpret_cast<size_t>(labels_out)) & 7) == 0,
-               "dn_merge_detections: boxes, boxes_out and the workspace must be 16-byte aligned, offsets and labels 8-byte aligned");
-    DN_REQUIRE(group_begin[0] >= 0 && group_begin[groups] <= s_total, "dn_merge_detections: group_begin spans sources %d .. %d of %d", group_begin[0],
-               group_begin[groups], s_total);
-    for (int g = 0; g < groups; ++g)
-        DN_REQUIRE(group_begin[g] <= group_begin[g + 1], "dn_merge_detections: group_begin decreases at group %d (%d > %d)", g, group_begin[g],
-                   group_begin[g + 1]);
     if (d > MG_MAX_D || d_out > MG_MAX_D || (long long)s_total * d > 0x7FFFFFFFll) {
         dn_set_error("dn_merge_detections: d=%d and d_out=%d at most %d, s_total * d below 2^31", d, d_out, MG_MAX_D);
         return DN_E_UNSUPPORTED;
@@ -401,20 +310,10 @@ extern "C" __attribute__((visibility("default"))) int dn_merge_detections(const 
     a.d = d; a.metric = metric; a.class_agnostic = class_agnostic; a.d_out = d_out; a.thresh = thresh; a.thresh_nonneg = thresh >= 0.f ? 1 : 0;
     a.boxes_out = reinterpret_cast<float4*>(boxes_out); a.scores_out = scores_out; a.labels_out = labels_out; a.counts_out = counts_out;
     a.src_out = src_out;
-    for (int g0 = 0; g0 < groups; g0 += MG_GROUPS) {
+    for (int g0 = 0; g0 < groups; g0 += DS_GROUPS) {
         GroupTab gt;
-        gt.count = groups - g0 < MG_GROUPS ? groups - g0 : MG_GROUPS;
-        gt.first = g0;
-        int slots = 0;
-        for (int g = 0; g <= MG_GROUPS; ++g) gt.begin[g] = group_begin[g0 + (g < gt.count ? g : gt.count)];
-        for (int g = 0; g < gt.count; ++g) slots = (gt.begin[g + 1] - gt.begin[g]) * d > slots ? (gt.begin[g + 1] - gt.begin[g]) * d : slots;
-        if (slots > 0) {
-            dn_note_kernel("merge_rank_kernel");
-            hipLaunchKernelGGL(merge_rank_kernel, dim3(dn_cdiv(slots, MG_NT), dn_cdiv(slots, MG_OTHERS), gt.count), dim3(MG_NT), 0, s, mb.keys, mb.rank, d,
-                               gt);
-            dn_note_kernel("merge_scatter_kernel");
-            hipLaunchKernelGGL(merge_scatter_kernel, dim3(dn_cdiv(slots, MG_NT), gt.count), dim3(MG_NT), 0, s, mb.keys, mb.rank, mb.order, d, gt);
-        }
+        const int slots = detset_chunk(group_begin, groups, g0, d, gt);
+        detset_rank(mb.keys, mb.rank, mb.order, d, gt, slots, s);
         dn_note_kernel("merge_walk_kernel");
         hipLaunchKernelGGL(merge_walk_kernel, dim3(gt.count), dim3(MG_NT), 0, s, a, gt);
     }

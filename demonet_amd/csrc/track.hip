@@ -14,7 +14,7 @@
 //   takes the r-th free slot in slot order.
 // Compiled with -ffp-contract=off: every operation of the header's text rounds once. No inline asm, no float atomics (the one atomic is an
 // unsigned maximum in LDS), no scratch.
-#include "common.h"
+#include "detset.h"
 
 namespace {
 
@@ -40,14 +40,10 @@ struct TrackArgs {
     int track_buffer, class_agnostic;
 };
 
-// IoU of a track's box a with a detection's box b: fp32, the operation order of dn_merge_detections (DN_MERGE_IOU, the track as a_i)
+// IoU of a track's box a with a detection's box b: the intersection is dn_merge_detections' own (dn_box_inter, the track as a_i), the rest its
+// DN_MERGE_IOU order
 __device__ __forceinline__ float tk_iou(const float4 a, const float4 b) {
-    const float xx1 = a.x > b.x ? a.x : b.x, yy1 = a.y > b.y ? a.y : b.y;
-    const float xx2 = a.z < b.z ? a.z : b.z, yy2 = a.w < b.w ? a.w : b.w;
-    float w = xx2 - xx1, h = yy2 - yy1;
-    if (w < 0.0f) w = 0.0f;
-    if (h < 0.0f) h = 0.0f;
-    const float inter = w * h;
+    const float inter = dn_box_inter(a, b);
     if (!(inter > 0.0f)) return -1.0f;      // u would be 0 or NaN: below every gate (the gates are >= 0), and the division is the costly part
     const float aa = (a.z - a.x) * (a.w - a.y);
     const float ab = (b.z - b.x) * (b.w - b.y);

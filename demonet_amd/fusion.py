@@ -17,7 +17,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .sliced import _stream, merge_detections
+from .sliced import _check_groups, _check_images, _check_tensors, _padded_outputs, _stream, merge_detections
 
 MAX_D = 512                 # rows per source, and rows per fused image
 MAX_SLOTS = 8192            # sources * rows per output image (the merge takes 65 536: the fusion walk is quadratic in the worst case)
@@ -54,23 +54,14 @@ def fuse_detections(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tenso
             (offsets, (S, 2), torch.float32)]
     if weights is not None:
         want.append((weights, (S,), torch.float32))
-    for t, shape, dtype in want:
-        if not isinstance(t, Tensor) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev or dev.type != "cuda":
-            raise ValueError("fuse_detections: expected a contiguous {} tensor of shape {} on the GPU, got {}".format(
-                dtype, shape, "{} {} on {}".format(t.dtype, tuple(t.shape), t.device) if isinstance(t, Tensor) else type(t)))
-    gb = [int(x) for x in group_begin]
+    _check_tensors("fuse_detections", want, dev)
+    gb, largest = _check_groups("fuse_detections", group_begin, S, d_out)
     G = len(gb) - 1
-    if G < 1 or d_out < 1 or gb[0] < 0 or gb[-1] > S or any(a > b for a, b in zip(gb, gb[1:])):
-        raise ValueError("fuse_detections: group_begin must hold groups + 1 ascending source indices in 0 .. {}, d_out >= 1".format(S))
-    check_fuse_limits(max(b - a for a, b in zip(gb, gb[1:])), max(d, d_out), "fuse_detections")
+    check_fuse_limits(largest, max(d, d_out), "fuse_detections")
     L = _lib.lib()
     gb_c = (C.c_int32 * (G + 1))(*gb)
     ws = torch.empty(L.dn_fuse_detections_workspace_bytes(S, d, gb_c, G), dtype=torch.uint8, device=dev)
-    ob = torch.empty((G, d_out, 4), dtype=torch.float32, device=dev)
-    os_ = torch.empty((G, d_out), dtype=torch.float32, device=dev)
-    ol = torch.empty((G, d_out), dtype=torch.int64, device=dev)
-    oc = torch.empty((G,), dtype=torch.int32, device=dev)
-    om = torch.empty((G, d_out), dtype=torch.int32, device=dev) if return_members else None
+    ob, os_, ol, oc, om = _padded_outputs(G, d_out, dev, return_members)
     p = C.c_void_p
     with torch.cuda.device(dev):
         _lib.check(L.dn_fuse_detections(p(boxes.data_ptr()), p(scores.data_ptr()), p(labels.data_ptr()), p(counts.data_ptr()), p(offsets.data_ptr()),
@@ -87,12 +78,7 @@ def _image_list(what: str, images) -> List[Tensor]:
         imgs = list(images.unbind(0))
     else:
         imgs = list(images)
-    for img in imgs:
-        if not isinstance(img, Tensor) or img.dim() != 3 or img.shape[0] != 3 or not img.is_floating_point():
-            raise ValueError("{}: images must be [3, H, W] float tensors, got {}".format(
-                what, (tuple(img.shape), img.dtype) if isinstance(img, Tensor) else type(img)))
-        if img.device != imgs[0].device:
-            raise ValueError("{}: all images must be on one device".format(what))
+    _check_images(what, imgs)
     return imgs
 
 

@@ -78,6 +78,39 @@ def check_merge_limits(sources: int, d: int, what: str = "merge"):
         raise ValueError("{}: {} sources x {} rows = {} slots for one image, the merge takes at most {}".format(what, sources, d, sources * d, MAX_SLOTS))
 
 
+# What merge_detections and fusion.fuse_detections check and allocate alike: S sources of d rows, grouped per output image by group_begin.
+def _check_tensors(what: str, want, dev):
+    """want: (tensor, shape, dtype) triples; every tensor contiguous, of that shape and dtype, on the GPU `dev`."""
+    for t, shape, dtype in want:
+        if not isinstance(t, Tensor) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev or dev.type != "cuda":
+            raise ValueError("{}: expected a contiguous {} tensor of shape {} on the GPU, got {}".format(
+                what, dtype, shape, "{} {} on {}".format(t.dtype, tuple(t.shape), t.device) if isinstance(t, Tensor) else type(t)))
+
+
+def _check_groups(what: str, group_begin: Sequence[int], S: int, d_out: int) -> Tuple[List[int], int]:
+    """-> (group_begin as ints, the sources of the largest group)"""
+    gb = [int(x) for x in group_begin]
+    if len(gb) < 2 or d_out < 1 or gb[0] < 0 or gb[-1] > S or any(a > b for a, b in zip(gb, gb[1:])):
+        raise ValueError("{}: group_begin must hold groups + 1 ascending source indices in 0 .. {}, d_out >= 1".format(what, S))
+    return gb, max(b - a for a, b in zip(gb, gb[1:]))
+
+
+def _padded_outputs(G: int, d_out: int, dev, extra: bool):
+    """-> boxes [G, d_out, 4], scores [G, d_out], labels [G, d_out], counts [G], and an int32 [G, d_out] (src, members) or None"""
+    return (torch.empty((G, d_out, 4), dtype=torch.float32, device=dev), torch.empty((G, d_out), dtype=torch.float32, device=dev),
+            torch.empty((G, d_out), dtype=torch.int64, device=dev), torch.empty((G,), dtype=torch.int32, device=dev),
+            torch.empty((G, d_out), dtype=torch.int32, device=dev) if extra else None)
+
+
+def _check_images(what: str, imgs):
+    for img in imgs:
+        if not isinstance(img, Tensor) or img.dim() != 3 or img.shape[0] != 3 or not img.is_floating_point():
+            raise ValueError("{}: images must be [3, H, W] float tensors, got {}".format(
+                what, (tuple(img.shape), img.dtype) if isinstance(img, Tensor) else type(img)))
+        if img.device != imgs[0].device:
+            raise ValueError("{}: all images must be on one device".format(what))
+
+
 def merge_detections(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tensor, offsets: Tensor, group_begin: Sequence[int], thresh: float,
                      metric: str = "iou", class_agnostic: bool = False, d_out: int = None, return_src: bool = False):
     """dn_merge_detections on tensors: boxes [S, d, 4] fp32, scores [S, d] fp32, labels [S, d] int64, counts [S] int32 (what forward_batch returns,
@@ -88,24 +121,14 @@ def merge_detections(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tens
     S, d = scores.shape
     d_out = d if d_out is None else int(d_out)
     dev = scores.device
-    want = ((boxes, (S, d, 4), torch.float32), (scores, (S, d), torch.float32), (labels, (S, d), torch.int64), (counts, (S,), torch.int32),
-            (offsets, (S, 2), torch.float32))
-    for t, shape, dtype in want:
-        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev or dev.type != "cuda":
-            raise ValueError("merge_detections: expected a contiguous {} tensor of shape {} on the GPU, got {} {} on {}".format(
-                dtype, shape, t.dtype, tuple(t.shape), t.device))
-    gb = [int(x) for x in group_begin]
+    _check_tensors("merge_detections", ((boxes, (S, d, 4), torch.float32), (scores, (S, d), torch.float32), (labels, (S, d), torch.int64),
+                                        (counts, (S,), torch.int32), (offsets, (S, 2), torch.float32)), dev)
+    gb, largest = _check_groups("merge_detections", group_begin, S, d_out)
     G = len(gb) - 1
-    if G < 1 or d_out < 1 or gb[0] < 0 or gb[-1] > S or any(a > b for a, b in zip(gb, gb[1:])):
-        raise ValueError("merge_detections: group_begin must hold groups + 1 ascending source indices in 0 .. {}, d_out >= 1".format(S))
-    check_merge_limits(max(b - a for a, b in zip(gb, gb[1:])), max(d, d_out), "merge_detections")
+    check_merge_limits(largest, max(d, d_out), "merge_detections")
     L = _lib.lib()
     ws = torch.empty(L.dn_merge_detections_workspace_bytes(S, d, G), dtype=torch.uint8, device=dev)
-    ob = torch.empty((G, d_out, 4), dtype=torch.float32, device=dev)
-    os_ = torch.empty((G, d_out), dtype=torch.float32, device=dev)
-    ol = torch.empty((G, d_out), dtype=torch.int64, device=dev)
-    oc = torch.empty((G,), dtype=torch.int32, device=dev)
-    src = torch.empty((G, d_out), dtype=torch.int32, device=dev) if return_src else None
+    ob, os_, ol, oc, src = _padded_outputs(G, d_out, dev, return_src)
     p = C.c_void_p
     with torch.cuda.device(dev):
         _lib.check(L.dn_merge_detections(p(boxes.data_ptr()), p(scores.data_ptr()), p(labels.data_ptr()), p(counts.data_ptr()), p(offsets.data_ptr()),
@@ -124,12 +147,7 @@ def detect_sliced(model, images, tile=None, overlap: float = 0.25, full_image: b
     imgs = [images] if single else list(images)
     if not imgs:
         return []
-    for img in imgs:
-        if not isinstance(img, Tensor) or img.dim() != 3 or img.shape[0] != 3 or not img.is_floating_point():
-            raise ValueError("detect_sliced: images must be [3, H, W] float tensors, got {}".format(
-                (tuple(img.shape), img.dtype) if isinstance(img, Tensor) else type(img)))
-        if img.device != imgs[0].device:
-            raise ValueError("detect_sliced: all images must be on one device")
+    _check_images("detect_sliced", imgs)
     if tile is None:
         tw0, th0 = model.graph.size
     elif isinstance(tile, int):

@@ -103,11 +103,19 @@ def merge_case(name):
         return dict(base, **_clustered(16, 64, 300, 5, 30, cnt), group_begin=[0, 64], d_out=300)
     if name == "i_shuffled":
         return dict(base, **_clustered(17, 5, 48, 3, 40, [48, 20, 48, 31, 7], shuffle=True), group_begin=[0, 5], d_out=60)
+    if name == "j_three_tables":
+        # 131 groups: the library hands the kernels 64 groups per launch, so three tables, the second and third with a first group > 0. Two sources
+        # of 4 rows per group on 3 centres (pairs across the sources overlap), ragged counts; group 64, the first of the second table, has no
+        # source; source 260 belongs to no group
+        gb = MANY_GROUPS
+        cnt = np.random.default_rng(18).integers(0, 5, gb[-1] + 1)
+        return dict(base, **_clustered(18, gb[-1] + 1, 4, 2, 3, cnt), group_begin=gb, d_out=6)
     raise KeyError(name)
 
 
+MANY_GROUPS = [2 * g for g in range(65)] + [2 * g for g in range(64, 131)]      # 132 entries; [64] == [65] == 128; ends at 260
 MERGE_CASES = ("a_identity", "b_two_tiles", "c_equal_scores", "d_chunks", "d_lattice", "e_empty_group", "f_agnostic", "g_nested_iou", "g_nested_ios",
-               "h_many_slots", "i_shuffled")
+               "h_many_slots", "i_shuffled", "j_three_tables")
 
 
 @functools.lru_cache(maxsize=None)
@@ -243,6 +251,13 @@ def test_every_gpu_merge_case_meets_its_input_condition(name):
         assert c["scores"].shape == (64, 300) and 0 < int(oc[0]) < 300
     if name == "i_shuffled":
         assert any(np.any(np.diff(c["scores"][s, :c["counts"][s]]) > 0) for s in range(5))
+    if name == "j_three_tables":
+        gb = c["group_begin"]
+        assert len(gb) - 1 == 131 and gb[64] == gb[65] and int(oc[64]) == 0 and gb[-1] < c["scores"].shape[0] and c["d_out"] > d
+        cand = np.array([c["counts"][a:b].sum() for a, b in zip(gb, gb[1:])])
+        for lo, hi in ((0, 64), (64, 128), (128, 131)):                           # every table keeps something and suppresses something
+            assert (oc[lo:hi] > 0).any() and (oc[lo:hi] < cand[lo:hi]).any(), (lo, hi)
+        assert len(set(c["counts"].tolist())) == 5                                # ragged: every count 0 .. 4
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

@@ -104,7 +104,15 @@ def case(name):
         c = _jittered(114, 1, 64, [64])
         return _case(np.concatenate([c["boxes"]] * 2), np.concatenate([c["scores"]] * 2), np.concatenate([c["labels"]] * 2),
                      offsets=np.concatenate([c["offsets"]] * 2))
-    if name.startswith("disjoint_"):    # one label, boxes that do not touch: clusters = candidates
+    if name == "three_tables":
+        # 131 groups: the library hands the kernels 64 groups per launch, so three tables, the second and third with a first group > 0. Two sources
+        # of 4 rows per group on 3 centres, ragged counts, unequal weights; group 64, the first of the second table, has no source; source 260
+        # belongs to no group
+        gb = [2 * g for g in range(65)] + [2 * g for g in range(64, 131)]
+        rng = np.random.default_rng(116)
+        return _jittered(116, gb[-1] + 1, 4, rng.integers(0, 5, gb[-1] + 1), n_centres=3, n_labels=2, group_begin=gb,
+                         weights=rng.choice([0.5, 1.0, 2.0, 3.0], gb[-1] + 1), d_out=6)
+    if name.startswith("disjoint_"):   # one label, boxes that do not touch: clusters = candidates
         n = int(name[9:])
         S, d = SIZES[n]
         rng = np.random.default_rng(n)
@@ -310,7 +318,7 @@ def _assert_same(want, got):
 
 
 SMALL = ("cf_pair", "cf_apart", "cf_single", "cf_on_thresh", "cf_labels", "cf_best") + tuple("ragged_{}".format(s) for s in SEEDS) + (
-    "nan_scores", "weights_skip", "two_groups_outside", "same_source_twice")
+    "nan_scores", "weights_skip", "two_groups_outside", "same_source_twice", "three_tables")
 
 
 @pytest.mark.gpu
@@ -322,6 +330,12 @@ def test_fuse_detections_equals_the_restatement_bit_for_bit(name):
         assert int(want[3][0]) > 0 and int(want[3][1]) == 0
     if name == "same_source_twice":
         assert (want[4][0, :int(want[3][0])] % 2 == 0).all()               # every box met its duplicate
+    if name == "three_tables":
+        gb, oc, om = c["group_begin"], want[3], want[4]
+        assert len(gb) - 1 == 131 and gb[64] == gb[65] and int(oc[64]) == 0 and gb[-1] < c["scores"].shape[0] and c["d_out"] > c["scores"].shape[1]
+        for lo, hi in ((0, 64), (64, 128), (128, 131)):                    # every table fuses a pair and leaves a box alone
+            assert (om[lo:hi] >= 2).any() and (om[lo:hi] == 1).any(), (lo, hi)
+        assert len(set(c["counts"].tolist())) == 5 and len(set(c["weights"].tolist())) == 4
     rc, got, _ = _fuse(c)
     assert rc == 0, _lib.lib().dn_last_error()
     _assert_same(want, got)
