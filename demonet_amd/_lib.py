@@ -10,6 +10,9 @@ DN_OP = dict(stem=1, pw=2, dw=3, se=4, conv=5, maxpool=6, l2norm=7)
 DN_T = dict(act=0, image=1, vec=2, pool=3)
 DN_NMS = dict(hard=0, linear=1, gaussian=2)
 DN_MERGE = dict(iou=0, ios=1)
+DN_FRAME = dict(nv12=0, i420=1, rgb24=2, bgr24=3)
+DN_COLOR = dict(bt601=0, bt709=1)
+DN_COLOR_FULL_RANGE = 0x10
 DN_SGD_CHUNK = 2048
 DN_SGD_MAX_GATE = 8
 
@@ -35,6 +38,10 @@ class SgdTensor(C.Structure):
 class SgdHyper(C.Structure):
     _fields_ = [("lr", C.c_float), ("momentum", C.c_float), ("dampening", C.c_float), ("weight_decay", C.c_float),
                 ("nesterov", C.c_int32), ("first_step", C.c_int32), ("step", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Frame(C.Structure):
+    _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_int32 * 3), ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32)]
 
 
 class TrackParams(C.Structure):
@@ -65,6 +72,8 @@ _SIGNATURES = {
                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dn_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dn_forward_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dn_forward_heads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dn_head_outputs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "dn_tensor_ptr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),

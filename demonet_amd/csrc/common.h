@@ -303,6 +303,9 @@ int launch_maxpool(const half_t* x, half_t* out, int n, int h, int w, int c, int
 int launch_l2norm(const half_t* x, const float* scale, half_t* out, long pixels, int c, hipStream_t s);
 // bilinear (align_corners=False) resize of NCHW fp32 planes; also writes scale_xy[n][2] = (w/ow, h/oh) in fp32
 int launch_u8hwc_to_planar(const unsigned char* in, float* out, float* scale_xy, int n, int h, int w, int oh, int ow, hipStream_t s);
+// dn_forward_frames: the record table is read on the device; DN_E_UNSUPPORTED for codes dn_frame_codes_known refuses
+bool dn_frame_codes_known(int format, int color);
+int launch_frames_to_planar(const dn_frame* frames, int format, int color, float* out, float* scale_xy, int n, int oh, int ow, hipStream_t s);
 int launch_resize_bilinear(const float* in, float* out, float* scale_xy, int n, int h, int w, int oh, int ow, hipStream_t s);
 
 // run of tiny layers (<= 32 output pixels each) executed by one workgroup per image with the activations in LDS (tail.hip)

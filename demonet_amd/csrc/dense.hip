@@ -133,6 +133,82 @@ __global__ __launch_bounds__(256) void u8hwc_kernel(const unsigned char* __restr
     }
 }
 
+// Video surfaces straight into the network input (dn_forward_frames, include/demonet_hip.h): one dn_frame record per image, read from
+// DEVICE memory at run time, every image with its own planes, pitches and size. Each of the four bilinear taps is converted to 8-bit RGB in
+// integer arithmetic as it is read (1 luma + 2 chroma bytes; chroma sample (x >> 1, y >> 1)); from there on the arithmetic is u8hwc_kernel's,
+// expression for expression, so the block equals what u8hwc_kernel writes from the converted frame, bit for bit.
+struct FrameColor { int cy, crv, cbu, cgu, cgv, yo; };       // round(c * 2^14), the luma offset (frame_color below)
+
+__device__ __forceinline__ int frame_clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+template <int FMT>
+__device__ __forceinline__ void frame_tap(const dn_frame& f, int x, int y, const FrameColor& k, float* rgb) {
+    int r, g, b;
+    if (FMT == DN_FRAME_RGB24 || FMT == DN_FRAME_BGR24) {
+        const uint8_t* p = f.plane[0] + (size_t)y * f.pitch[0] + (size_t)x * 3;
+        r = p[FMT == DN_FRAME_RGB24 ? 0 : 2]; g = p[1]; b = p[FMT == DN_FRAME_RGB24 ? 2 : 0];
+    } else {
+        const int yy = (int)f.plane[0][(size_t)y * f.pitch[0] + x] - k.yo;
+        int u, v;
+        if (FMT == DN_FRAME_NV12) {
+            const uint8_t* p = f.plane[1] + (size_t)(y >> 1) * f.pitch[1] + (size_t)(x >> 1) * 2;
+            u = (int)p[0] - 128; v = (int)p[1] - 128;
+        } else {
+            u = (int)f.plane[1][(size_t)(y >> 1) * f.pitch[1] + (x >> 1)] - 128;
+            v = (int)f.plane[2][(size_t)(y >> 1) * f.pitch[2] + (x >> 1)] - 128;
+        }
+        const int l = k.cy * yy + (1 << 13);
+        r = frame_clamp8((l + k.crv * v) >> 14);                    // >> of a signed int: arithmetic (floor)
+        g = frame_clamp8((l - k.cgu * u - k.cgv * v) >> 14);
+        b = frame_clamp8((l + k.cbu * u) >> 14);
+    }
+    rgb[0] = (float)r / 255.f; rgb[1] = (float)g / 255.f; rgb[2] = (float)b / 255.f;
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void frames_kernel(const dn_frame* __restrict__ frames, float* __restrict__ out, float* __restrict__ scale_xy,
+                                                     int n, int oh, int ow, FrameColor k) {
+    long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const int ox = (int)(idx % ow);
+    idx /= ow;
+    const int oy = (int)(idx % oh);
+    const long img = idx / oh;
+    if (img >= n) return;
+    const dn_frame f = frames[img];
+    const int h = f.height, w = f.width;
+    if (ox == 0 && oy == 0) {       // always: a ratio of exactly 1 maps the boxes back unchanged
+        scale_xy[2 * img] = (float)w / (float)ow;
+        scale_xy[2 * img + 1] = (float)h / (float)oh;
+    }
+    const float rh = (float)h / (float)oh, rw = (float)w / (float)ow;
+    const float sy = fmaxf(rh * ((float)oy + 0.5f) - 0.5f, 0.f);
+    const float sx = fmaxf(rw * ((float)ox + 0.5f) - 0.5f, 0.f);
+    const int y0 = (int)sy, x0 = (int)sx;
+    const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
+    const float ly = fminf(fmaxf(sy - (float)y0, 0.f), 1.f), lx = fminf(fmaxf(sx - (float)x0, 0.f), 1.f);
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    float a[3], b[3], cc[3], d[3];
+    frame_tap<FMT>(f, x0, y0, k, a);
+    frame_tap<FMT>(f, x1, y0, k, b);
+    frame_tap<FMT>(f, x0, y1, k, cc);
+    frame_tap<FMT>(f, x1, y1, k, d);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        out[(((size_t)img * 3 + c) * oh + oy) * ow + ox] = bilerp(a[c], b[c], cc[c], d[c], hx, lx, hy, ly);
+}
+
+// round(c * 2^14) of cy = 255/219, crv = 2(1 - Kr) cs, cbu = 2(1 - Kb) cs, cgu = 2 Kb (1 - Kb) / Kg cs, cgv = 2 Kr (1 - Kr) / Kg cs with
+// cs = 255/224, yo = 16 (limited range) or cy = cs = 1, yo = 0 (full range); BT.601: Kr, Kb = 0.299, 0.114, BT.709: 0.2126, 0.0722
+// (tests/frames_ref.py derives the same integers from Kr, Kb in float64)
+bool frame_color(int color, FrameColor* k) {
+    const bool full = (color & DN_COLOR_FULL_RANGE) != 0;
+    switch (color & ~DN_COLOR_FULL_RANGE) {
+        case DN_COLOR_BT601: *k = full ? FrameColor{16384, 22970, 29032, 5638, 11700, 0} : FrameColor{19077, 26149, 33050, 6419, 13320, 16}; return true;
+        case DN_COLOR_BT709: *k = full ? FrameColor{16384, 25802, 30402, 3069, 7670, 0} : FrameColor{19077, 29372, 34610, 3494, 8731, 16}; return true;
+    }
+    return false;
+}
+
 }  // namespace
 
 int launch_maxpool(const half_t* x, half_t* out, int n, int h, int w, int c, int k, int stride, int pad, int ho, int wo,
@@ -161,6 +237,29 @@ int launch_u8hwc_to_planar(const unsigned char* in, float* out, float* scale_xy,
     const long threads = (long)n * oh * ow;
     dn_note_kernel("u8hwc_kernel");
     hipLaunchKernelGGL(u8hwc_kernel, dim3(dn_cdiv(threads, 256)), dim3(256), 0, s, in, out, scale_xy, n, h, w, oh, ow);
+    return DN_OK;
+}
+
+bool dn_frame_codes_known(int format, int color) {
+    FrameColor k;
+    return format >= DN_FRAME_NV12 && format <= DN_FRAME_BGR24 && color >= 0 && frame_color(color, &k);
+}
+
+int launch_frames_to_planar(const dn_frame* frames, int format, int color, float* out, float* scale_xy, int n, int oh, int ow, hipStream_t s) {
+    FrameColor k;
+    if (!dn_frame_codes_known(format, color) || !frame_color(color, &k)) {
+        dn_set_error("frames: unknown format %d or colour code 0x%x", format, color);
+        return DN_E_UNSUPPORTED;
+    }
+    const long threads = (long)n * oh * ow;
+    const dim3 grid(dn_cdiv(threads, 256)), block(256);
+    dn_note_kernel("frames_kernel<%d>", format);
+    switch (format) {
+        case DN_FRAME_NV12: hipLaunchKernelGGL(frames_kernel<DN_FRAME_NV12>, grid, block, 0, s, frames, out, scale_xy, n, oh, ow, k); break;
+        case DN_FRAME_I420: hipLaunchKernelGGL(frames_kernel<DN_FRAME_I420>, grid, block, 0, s, frames, out, scale_xy, n, oh, ow, k); break;
+        case DN_FRAME_RGB24: hipLaunchKernelGGL(frames_kernel<DN_FRAME_RGB24>, grid, block, 0, s, frames, out, scale_xy, n, oh, ow, k); break;
+        default: hipLaunchKernelGGL(frames_kernel<DN_FRAME_BGR24>, grid, block, 0, s, frames, out, scale_xy, n, oh, ow, k); break;
+    }
     return DN_OK;
 }
 

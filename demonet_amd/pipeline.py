@@ -23,7 +23,7 @@ from .ssd import _require_floating, forward_args
 
 
 class _Slot:
-    __slots__ = ("stream", "images", "ws", "boxes", "scores", "labels", "counts", "packed", "done", "args")
+    __slots__ = ("stream", "images", "ws", "boxes", "scores", "labels", "counts", "packed", "done", "args", "table", "frames")
 
 
 _STREAMS = {}
@@ -43,7 +43,9 @@ def _slot_stream(device, slot: int):
 
 class ForwardPipeline:
     """`depth` forwards of `model` in flight on `device`, for batches of a fixed shape [batch, 3, height, width] (fp32 in [0, 1]) or,
-    with uint8=True, [batch, height, width, 3] uint8 (a decoder's output, `SSD.forward_uint8`).
+    with uint8=True, [batch, height, width, 3] uint8 (a decoder's output, `SSD.forward_uint8`), or, with frames=(format, matrix, full_range),
+    for `frames.FrameBatch`es of `batch` video surfaces of any sizes (`SSD.forward_frames`): every slot owns a record table, submit(batch)
+    copies the batch's records into it on the slot's stream and the slot keeps the surfaces alive until it is submitted to again.
 
         pipe = ForwardPipeline(model, batch=64, depth=3)
         t = pipe.submit(images)                 # returns at once; the forward runs on the slot's own stream
@@ -56,12 +58,20 @@ class ForwardPipeline:
     """
 
     def __init__(self, model, batch: int, height: Optional[int] = None, width: Optional[int] = None, depth: int = 3, chains: int = 1,
-                 device="cuda:0", uint8: bool = False, packed: bool = False):
+                 device="cuda:0", uint8: bool = False, packed: bool = False, frames=None):
         if depth < 1 or depth > 16:
             raise ValueError("depth must be in [1, 16], got {}".format(depth))
         if batch < 1:
             raise ValueError("batch must be positive")
         device = torch.device(device)
+        self._frames = None
+        if frames is not None:
+            from .frames import codes
+            if uint8 or height is not None or width is not None:
+                raise ValueError("frames= excludes uint8, height and width: every frame of a FrameBatch has its own size")
+            if not isinstance(frames, (tuple, list)) or len(frames) != 3:
+                raise ValueError("frames must be (format, matrix, full_range), got {!r}".format(frames))
+            self._frames = codes(*frames)
         W, H = model.graph.size
         self.model, self.device, self.depth, self.batch, self.uint8 = model, device, int(depth), int(batch), bool(uint8)
         self.h, self.w = int(height or H), int(width or W)
@@ -79,14 +89,21 @@ class ForwardPipeline:
         D = model.detections_per_img
         self._fwd = L.dn_forward_u8 if uint8 else L.dn_forward
         self._name = "dn_forward_u8" if uint8 else "dn_forward"
+        if self._frames is not None:
+            self._fwd, self._name = L.dn_forward_frames, "dn_forward_frames"
         self.slots = []
         with torch.cuda.device(device):
             ws_bytes = L.dn_workspace_bytes(C.c_void_p(self._handle), batch)
             for _ in range(depth):
                 s = _Slot()
                 s.stream = _slot_stream(device, len(self.slots))
-                s.images = (torch.empty((batch, self.h, self.w, 3), dtype=torch.uint8, device=device) if uint8
-                            else torch.empty((batch, 3, self.h, self.w), dtype=torch.float32, device=device))
+                s.table = s.frames = None
+                if self._frames is not None:
+                    s.images = None
+                    s.table = torch.empty(batch * C.sizeof(_lib.Frame), dtype=torch.uint8, device=device)
+                else:
+                    s.images = (torch.empty((batch, self.h, self.w, 3), dtype=torch.uint8, device=device) if uint8
+                                else torch.empty((batch, 3, self.h, self.w), dtype=torch.float32, device=device))
                 s.ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
                 s.boxes = torch.empty((batch, D, 4), dtype=torch.float32, device=device)
                 s.scores = torch.empty((batch, D), dtype=torch.float32, device=device)
@@ -102,7 +119,8 @@ class ForwardPipeline:
     # ------------------------------------------------------------------------------------------------------
     def _args(self, s, src_ptr):
         if s.args is None or s.args[1].value != src_ptr:
-            s.args = forward_args(self._handle, src_ptr, self.batch, self.h, self.w, (s.boxes, s.scores, s.labels, s.counts), s.ws, s.stream.cuda_stream)
+            a, b = self._frames if self._frames is not None else (self.h, self.w)       # (dn_forward_frames: format and colour where h and w stand)
+            s.args = forward_args(self._handle, src_ptr, self.batch, a, b, (s.boxes, s.scores, s.labels, s.counts), s.ws, s.stream.cuda_stream)
         return s.args
 
     def submit(self, images: Tensor, persistent_input: bool = False) -> int:
@@ -120,6 +138,8 @@ class ForwardPipeline:
                 raise RuntimeError("the model's weights changed since the plan was lowered: close this pipeline and build a new one")
             self.model._remember_weights(self.device)      # only the structure epoch moved (another model was built): back to the cheap test
         s = self.slots[self.n % self.depth]
+        if self._frames is not None:
+            return self._submit_frames(s, images)
         if tuple(images.shape) != tuple(s.images.shape):
             raise ValueError("expected a batch of shape {}, got {}".format(tuple(s.images.shape), tuple(images.shape)))
         if self.uint8:
@@ -138,6 +158,34 @@ class ForwardPipeline:
             images.record_stream(s.stream)
         args = self._args(s, images.data_ptr() if direct else s.images.data_ptr())
         self.model._set_packed(s.packed)            # (the plan is the model's own: checked above)
+        with torch.cuda.device(self.device):
+            _lib.check(self._fwd(*args), self._name)
+        s.done.record(s.stream)
+        t = self.n
+        self.n += 1
+        return t
+
+    def _submit_frames(self, s, batch) -> int:
+        from .frames import FrameBatch
+        if not isinstance(batch, FrameBatch):
+            raise ValueError("this pipeline takes FrameBatches (frames=...), got {}".format(type(batch).__name__))
+        if batch.n != self.batch:
+            raise ValueError("expected a FrameBatch of {} frames, got {}".format(self.batch, batch.n))
+        if batch.device != self.device:
+            raise ValueError("the FrameBatch is on {}, the pipeline on {}".format(batch.device, self.device))
+        if (batch.format_code, batch.color_code) != self._frames:
+            raise ValueError("the FrameBatch is {} / {}{}, the pipeline was built for other codes".format(batch.format, batch.matrix, " full range" if batch.full_range else ""))
+        if batch._host is None:
+            raise ValueError("the FrameBatch names no frames yet: call set() first")
+        # the slot's previous outputs may be overwritten now, and the surfaces must be complete: order after the caller's stream
+        s.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s.stream):
+            s.table.copy_(batch._host, non_blocking=True)      # n * 48 bytes from the pinned records of batch.set(): the batch may be set again at once
+        s.frames = batch.frames                                 # alive until this slot's next submit ...
+        for t in batch.planes:                                  # ... and their memory is not handed out again before this forward has read it
+            t.record_stream(s.stream)
+        args = self._args(s, s.table.data_ptr())
+        self.model._set_packed(s.packed)
         with torch.cuda.device(self.device):
             _lib.check(self._fwd(*args), self._name)
         s.done.record(s.stream)

@@ -400,6 +400,21 @@ class SSD(_Tracked):
         from .track import track
         return track(self, images, tracker)
 
+    def forward_frames(self, batch, packed: Optional[Tensor] = None):
+        """The forward on video surfaces (demonet_amd/frames.py): batch is a FrameBatch naming n NV12 / I420 / RGB24 / BGR24 frames, each
+        its own allocation with its own pitches and its own SIZE. The colour conversion (integer arithmetic fixed in include/demonet_hip.h,
+        dn_forward_frames), /255, the bilinear resize and the planar layout run as one pass ahead of the stem, reading four taps per network
+        pixel; no converted frame and no float staging image exist. Results equal forward_uint8 of the frames converted by those formulas, bit
+        for bit; boxes are in each frame's own pixel coordinates. The graph replays on whatever frames batch.set() named last.
+        Returns the padded device tensors of forward_batch. ValueError for a batch without frames or on another device than the model."""
+        from .frames import forward_frames
+        return forward_frames(self, batch, packed)
+
+    def track_frames(self, batch, tracker):
+        """`track` on top of forward_frames: frame b of the FrameBatch is the current frame of stream b. Returns what ByteTracker.update returns."""
+        from .frames import track_frames
+        return track_frames(self, batch, tracker)
+
     def batch_split(self, n: int) -> int:
         """Number of parallel sub-batch launch chains a forward of n images is issued as (1 = a single chain)."""
         if self._handle is None:

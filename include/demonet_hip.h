@@ -106,6 +106,35 @@ DN_API int dn_forward_u8(dn_plan* plan, const uint8_t* images_dev, int n, int h,
                   float* boxes_dev, float* scores_dev, int64_t* labels_dev, int32_t* counts_dev,
                   void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The same with video surfaces as input, as decoders hand them out: one record per image, every image with its own allocation(s), row
+ * pitches and SIZE (720p and 1080p cameras mix in one batch). Each bilinear tap of the resize is converted to 8-bit RGB as it is read, in
+ * integer arithmetic fixed here; from there on the arithmetic is dn_forward_u8's, so the network input equals, bit for bit, what dn_forward_u8
+ * computes from the frame converted by these formulas. With y = Y - yo, u = U - 128, v = V - 128:
+ *     R = clamp((cy y + crv v + 2^13) >> 14),  G = clamp((cy y - cgu u - cgv v + 2^13) >> 14),  B = clamp((cy y + cbu u + 2^13) >> 14)
+ * (>> arithmetic, i.e. floor; clamp to 0 .. 255), every coefficient round(c 2^14) of cy = 255/219, crv = 2(1 - Kr) cs, cbu = 2(1 - Kb) cs,
+ * cgu = 2 Kb (1 - Kb) / Kg cs, cgv = 2 Kr (1 - Kr) / Kg cs, with cs = 255/224 and yo = 16 for limited range (16..235 / 16..240) and
+ * cy = cs = 1, yo = 0 for full range; BT.601: Kr, Kb = 0.299, 0.114, BT.709: 0.2126, 0.0722 (Kg = 1 - Kr - Kb).
+ * Chroma is NOT interpolated: the chroma sample of pixel (x, y) is (x >> 1, y >> 1), nearest replication as the common fast converters do.
+ * DN_FRAME_RGB24 / DN_FRAME_BGR24 skip the conversion (`color` is still checked). */
+enum { DN_FRAME_NV12 = 0, DN_FRAME_I420 = 1, DN_FRAME_RGB24 = 2, DN_FRAME_BGR24 = 3 };
+enum { DN_COLOR_BT601 = 0, DN_COLOR_BT709 = 1, DN_COLOR_FULL_RANGE = 0x10 };      /* matrix | DN_COLOR_FULL_RANGE: full range; otherwise limited */
+typedef struct dn_frame {                                  /* 48 bytes, one per image, in DEVICE memory */
+    const uint8_t* plane[3];   /* NV12: Y, interleaved UV, unused; I420: Y, U, V; RGB24/BGR24: packed pixels, unused, unused */
+    int32_t pitch[3];          /* bytes per row of each plane (>= the row's payload) */
+    int32_t width, height;     /* of THIS frame; chroma planes are ceil(height/2) rows of ceil(width/2) samples */
+    int32_t reserved;
+} dn_frame;
+/* frames_dev = [n] records in device memory, read by the first kernel of the forward WHEN IT RUNS: a captured graph is keyed on the table's
+ * address (with n, format, color and the output pointers) and replays on whatever surfaces the table names at that moment -- putting a new
+ * frame into the table (an ordinary copy on `stream` ahead of the call) needs no recapture. Outputs and asynchrony are dn_forward's; boxes
+ * come back in each frame's own pixel coordinates.
+ * TRUST BOUNDARY: the library cannot inspect a device table. It trusts every record: plane pointers valid for pitch * rows bytes, pitches
+ * and sizes positive; a wrong record is an out-of-bounds device read. Validate on the host before the records go up (Python: FrameBatch.set).
+ * DN_E_INVALID for a null table or n <= 0, DN_E_UNSUPPORTED for an unknown format or colour code. */
+DN_API int dn_forward_frames(dn_plan* plan, const dn_frame* frames_dev, int n, int format, int color,
+                      float* boxes_dev, float* scores_dev, int64_t* labels_dev, int32_t* counts_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Backbone + heads only (no post-process). The head outputs live inside the workspace; query them with
  * dn_head_outputs:  cls_logits [n][A][K] fp32, bbox_regression [n][A][4] fp32 (generalized_ssd.py:60-74). Valid after
  * dn_forward_heads only: dn_forward may compute softmax / box decode inside the head launch and then never writes the logits
