@@ -121,10 +121,10 @@ _CACHE = {}
 
 
 def _run(cfg, weights=None):
-    key = _cid(cfg) + (f"-{weights}" if weights else "")
+    name, ncls, n, env, size = cfg
+    key = _cid(cfg) + f"-K{ncls}" + (f"-{weights}" if weights else "")         # (the test ids leave the class count out; the results must not)
     if key in _CACHE:
         return _CACHE[key]
-    name, ncls, n, env, size = cfg
     dev = torch.device("cuda:0")
     L = _lib.lib()
     t0 = time.time()
