@@ -130,6 +130,13 @@ _SIGNATURES = {
     "dn_track_update": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(TrackParams), C.c_void_p, C.c_size_t] + [C.c_void_p] * 8),
 }
 EXPORTS = tuple(_SIGNATURES)
+# include/demonet_hip_debug.h: test support beside the boundary (not part of EXPORTS, which mirrors demonet_hip.h)
+_DEBUG_SIGNATURES = {
+    "dn_debug_last_kernel": (C.c_int, [C.c_char_p, C.c_int]),
+    "dn_debug_conv_pool": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_void_p]),
+    "dn_debug_stem": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p]),
+    "dn_debug_choice": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.c_int, C.c_char_p, C.c_int]),
+}
 
 _lib = None
 
@@ -148,7 +155,7 @@ def lib():
             f"{LIB_PATH} not found: build it with `python -m demonet_amd.build` (hipcc, gfx950). "
             "demonet_amd has no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_DEBUG_SIGNATURES.items()):
         fn = getattr(L, name)          # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -163,3 +170,22 @@ def check(rc: int, what: str = ""):
         msg = lib().dn_last_error().decode("utf-8", "replace")
         raise RuntimeError(f"demonet_hip {what} failed ({rc}): {msg}")
     return rc
+
+
+def debug_last_kernel() -> str:
+    """Label of the kernel the last launcher call on this thread enqueued (dn_debug_last_kernel)."""
+    buf = C.create_string_buffer(128)
+    check(lib().dn_debug_last_kernel(buf, len(buf)), "dn_debug_last_kernel")
+    return buf.value.decode()
+
+
+def debug_choice(family: str, *dims) -> dict:
+    """What the kernel-choice functions answer for a shape (dn_debug_choice; host only): the "key=value" text as a dict, integers as int."""
+    arr = (C.c_int64 * len(dims))(*[int(v) for v in dims])
+    buf = C.create_string_buffer(256)
+    check(lib().dn_debug_choice(family.encode(), arr, len(dims), buf, len(buf)), "dn_debug_choice")
+    out = {}
+    for item in buf.value.decode().split():
+        k, v = item.split("=", 1)
+        out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out

@@ -72,6 +72,9 @@ __device__ __forceinline__ void fma_mix_h8(float (&acc)[8], const uint4& e, cons
 }
 
 static inline int dn_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// The launchers count the rows of a problem (images x pixels) in an int, and with the XCD grouping (common.h below) the kernels form the row 8 xq hw <= (n + 7) hw:
+// every entry that turns images into rows asks this first.
+static inline bool dn_rows_fit(long images, long rows_per_image) { return images > 0 && rows_per_image > 0 && (images + 7) * rows_per_image < (1L << 31); }
 static inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }      // workspace carving: every array starts on a 256-byte boundary
 
 // Environment knob, read on EVERY call -- never latched in a static -- so that a test can A/B two settings in one process
@@ -206,6 +209,7 @@ bool conv_patch_pool_ok(int cin, int cout, int h, int w);       // on the patch 
 bool conv_halo_pool_ok(int cin, int cout, int h, int w);        // on the run-staged 256 x 256 tile: may also write the conv output itself (a.out set)
 bool conv_pool_ok(int cin, int cout, int h, int w);             // either
 int launch_conv_pool(const PwArgs& a, hipStream_t s);          // a.pool_out set
+long conv_patch_resident_blocks(int n, int h, int w);         // workgroup blocks of conv_patch_resident_kernel (its launcher refuses 2^30 or more)
 // dense fp32 head (with or without a rider in w_b) on the run-staged tiles
 bool conv_head_big_supported(const PwArgs& a);
 int launch_conv_head_big(const PwArgs& a, hipStream_t s);

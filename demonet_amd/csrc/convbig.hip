@@ -1132,7 +1132,7 @@ __global__ __launch_bounds__(256) void conv_patch_resident_kernel(PwArgs a, int 
 
 int launch_patch_resident(const PwArgs& a, hipStream_t s) {
     const int tiles_x = dn_cdiv(a.cv_w, PT), tiles = tiles_x * dn_cdiv(a.cv_h, PT);
-    const long ntiles = (long)tiles * (a.m / a.hw);
+    const long ntiles = conv_patch_resident_blocks(a.m / a.hw, a.cv_h, a.cv_w);
     DN_REQUIRE(ntiles < (1L << 30), "conv_patch_resident_kernel: %ld blocks", ntiles);
     const int groups = a.cout / 64;
     int g = (256 / groups) & ~7;                                  // one workgroup per CU in all (256 CUs), a multiple of the 8 XCDs per channel group
@@ -1173,6 +1173,9 @@ int launch_halo(const PwArgs& a, hipStream_t s, const char* name) {
     return DN_OK;
 }
 }  // namespace
+
+// 16 x 16 output blocks of a conv_patch_resident_kernel launch (the kernel takes the count as an int and splits it over the 8 XCDs: the launcher keeps it below 2^30)
+long conv_patch_resident_blocks(int n, int h, int w) { return (long)dn_cdiv(w, PT) * dn_cdiv(h, PT) * n; }
 
 // the convbig.hip arms of the dense-conv launchers' switch (choice.h: conv_choose)
 int launch_conv_big(const PwArgs& a, const PwChoice& c, hipStream_t s) {

@@ -418,7 +418,8 @@ bool dw_fill(DwArgs& a, const int tw) {
     a.fd_c8 = fastdiv(c8);
     a.fd_xs = fastdiv(xs);
     const unsigned long long threads = (unsigned long long)a.ho * xs * c8 + 256;
-    return fd_ok(threads, c8) && fd_ok(threads / c8 + 1, xs) && (unsigned long long)a.h * a.w_ * a.c < 0x80000000ull;
+    // (the output row index n * ho + oy of dw_body is an int)
+    return fd_ok(threads, c8) && fd_ok(threads / c8 + 1, xs) && (unsigned long long)a.h * a.w_ * a.c < 0x80000000ull && (unsigned long long)a.n * a.ho < 0x80000000ull;
 }
 int dw_blocks(const DwArgs& a, const int tw) { return dn_cdiv((long)a.ho * ((a.wo + tw - 1) / tw) * (a.c / 8), 256); }      // workgroups per image
 
@@ -464,6 +465,7 @@ int launch_dw_group(const DwArgs* arr, int count, hipStream_t s) {
         acc += g.nblocks[i] * (arr[i].xq > 0 ? 8 : 1);
     }
     g.start[count] = acc;
+    DN_REQUIRE((arr[0].xq > 0 ? arr[0].xq : arr[0].n) <= 65535, "depthwise group: %d images: more than 65535 image slots on grid.y", arr[0].n);
     dn_note_kernel("dw_group_kernel<%d,%d,%d>", K, S, TW);
     hipLaunchKernelGGL((dw_group_kernel<K, S, TW>), dim3(acc, arr[0].xq > 0 ? arr[0].xq : arr[0].n), dim3(256), 0, s, g);
     return DN_OK;
@@ -472,7 +474,8 @@ int launch_dw_group(const DwArgs* arr, int count, hipStream_t s) {
 template <int K, int S, int TW>
 int launch_dw(const DwArgs& a0, const DwChoice::Pool pool, hipStream_t s) {
     DwArgs a = a0;
-    DN_REQUIRE(dw_fill(a, TW), "depthwise: %d x %d x %d outside the index range of the kernel", a.ho, a.wo, a.c);
+    DN_REQUIRE(dw_fill(a, TW), "depthwise: %d x %d x %d outside the index range of the kernel (h w c of an image and n ho below 2^31, the thread index inside the fast division)", a.ho, a.wo, a.c);
+    DN_REQUIRE((a.xq > 0 ? a.xq : a.n) <= 65535, "depthwise: %d images%s: more than 65535 image slots on grid.y", a.n, a.xq > 0 ? " in 8 groups" : "");
     dn_note_kernel("dw_kernel<%d,%d,%d>", K, S, TW);
     const int nblocks = dw_blocks(a, TW);
     const dim3 grid = xcd_grid2(nblocks, a.xq, a.n);
@@ -1396,6 +1399,13 @@ int launch_depthwise_group(const DwArgs* arr, int count, hipStream_t s) {
                    arr[i].xq == arr[0].xq, "depthwise group: problem %d is not compatible (one k, stride and batch, no pooled output)", i);
     }
     return dw_dispatch(dw_choose(arr[0]), [&](auto i) { using I = decltype(i); return launch_dw_group<I::K, I::S, I::TW>(arr, count, s); });
+}
+
+// dn_debug_choice: the two addressing limits of a depthwise launch as the launcher applies them (dw_fill, dw_wlds_bytes)
+void depthwise_debug_limits(const DwArgs& a0, int tw, bool* in_range, size_t* wlds_bytes) {
+    DwArgs a = a0;
+    *in_range = dw_fill(a, tw);
+    *wlds_bytes = dw_wlds_bytes(a, a.k);
 }
 
 int depthwise_pool_blocks(const DwArgs& a) {

@@ -416,6 +416,7 @@ int ssd_loss_launch(const char* who, const float* cls_logits, const float* bbox_
     DN_REQUIRE(cls_logits && bbox_regression && anchors && gt_boxes && gt_labels && gt_counts && losses && workspace, "%s: null argument", who);
     DN_REQUIRE(n > 0 && num_anchors > 0 && num_classes >= 2 && gmax >= 1 && gmax <= GMAX, "%s: bad sizes n=%d A=%d K=%d gmax=%d (gmax <= %d)", who, n,
                num_anchors, num_classes, gmax, GMAX);
+    DN_REQUIRE(n <= 65535 && (long long)n * num_anchors < (1LL << 31), "%s: n=%d above 65535 (the image is on grid.y), or n * num_anchors of 2^31 rows or more (int row indices)", who, n);
     DN_REQUIRE(workspace_bytes >= dn_ssd_loss_workspace_bytes(n, num_anchors), "%s: workspace %zu B too small", who, workspace_bytes);
     DN_REQUIRE((reinterpret_cast<size_t>(anchors) & 15) == 0 && (reinterpret_cast<size_t>(gt_boxes) & 15) == 0 && (reinterpret_cast<size_t>(bbox_regression) & 15) == 0,
                "%s: box arrays must be 16-byte aligned", who);
@@ -482,6 +483,7 @@ extern "C" __attribute__((visibility("default"))) int dn_ssd_loss_backward(const
     DN_REQUIRE((!grad_cls_logits || cls_logits) && (!grad_bbox_regression || bbox_regression), "dn_ssd_loss_backward: a gradient is asked for an input that is null");
     DN_REQUIRE(n > 0 && num_anchors > 0 && num_classes >= 2 && gmax >= 1 && gmax <= GMAX, "dn_ssd_loss_backward: bad sizes n=%d A=%d K=%d gmax=%d (gmax <= %d)",
                n, num_anchors, num_classes, gmax, GMAX);
+    DN_REQUIRE((long long)n * num_anchors < (1LL << 31), "dn_ssd_loss_backward: n * num_anchors of 2^31 rows or more (int row indices)");
     DN_REQUIRE(state_bytes >= dn_ssd_loss_state_bytes(n, num_anchors) && (reinterpret_cast<size_t>(state) & 15) == 0,
                "dn_ssd_loss_backward: state misaligned or too small (%zu B)", state_bytes);
     DN_REQUIRE(((reinterpret_cast<size_t>(anchors) | reinterpret_cast<size_t>(gt_boxes) | reinterpret_cast<size_t>(bbox_regression) |

@@ -1308,6 +1308,13 @@ static int forward_impl(dn_plan* p, const void* images, int n, int h, int w, flo
     } busy(p->in_call);
     DN_REQUIRE(busy.ok, "dn_forward: the plan is in use by another host thread (one plan serves one thread at a time; use one plan per thread)");
     DN_REQUIRE(heads_only || (boxes && scores && labels && counts), "dn_forward: null output buffer");
+    {   // the launchers count the rows of a chain's tensors (images x pixels) in an int, the XCD grouping rounds the chain up to 8 groups of images
+        const int S0 = batch_split(p, n);
+        const long per_chain = (n + S0 - 1) / S0;
+        for (const dn_tensor_desc& t : p->tensors)
+            DN_REQUIRE((t.kind != DN_T_ACT && t.kind != DN_T_IMAGE) || dn_rows_fit(per_chain, (long)t.h * t.w),
+                       "dn_forward: %ld images per chain of %d x %d pixels are 2^31 rows or more", per_chain, t.h, t.w);
+    }
     const Layout& L = get_layout(p, n);
     if (ws_bytes < L.total) {
         dn_set_error("dn_forward: workspace %zu B < required %zu B for n=%d", ws_bytes, L.total, n);
@@ -1653,4 +1660,189 @@ extern "C" int dn_depthwise_conv_pool(const void* x, const void* w, const float*
     if (rc) return rc;
     DN_HIP_CHECK(hipGetLastError());
     return DN_OK;
+}
+
+// ---- test support (include/demonet_hip_debug.h): which kernel a stand-alone call took, the image-range loop of launch_conv_pool without a
+// model around it, and the choice functions of choice.h asked about a shape on a machine without a GPU
+extern "C" __attribute__((visibility("default"))) int dn_debug_last_kernel(char* buf, int capacity) {
+    DN_REQUIRE(buf && capacity > 0, "dn_debug_last_kernel: no buffer");
+    snprintf(buf, (size_t)capacity, "%s", dn_last_kernel());
+    return DN_OK;
+}
+
+extern "C" __attribute__((visibility("default"))) int dn_debug_conv_pool(const void* x, const void* w, const float* bias, const void* zeros, void* pool_out,
+                                                                        void* out, int n, int h, int wd, int cin, int cout, int act, void* stream) {
+    DN_REQUIRE(x && w && bias && pool_out, "dn_debug_conv_pool: null argument");
+    DN_REQUIRE(n > 0 && h > 0 && wd > 0 && dn_rows_fit(n, (long)h * wd), "dn_debug_conv_pool: bad geometry, or 2^31 rows or more");
+    DN_REQUIRE(cin % 32 == 0 && cout % 4 == 0, "dn_debug_conv_pool: cin=%d must be a multiple of 32, cout=%d of 4", cin, cout);
+    ConvArgs c;
+    c.x = reinterpret_cast<const half_t*>(x); c.w = reinterpret_cast<const half_t*>(w); c.bias = bias; c.out = out;
+    c.zeros = reinterpret_cast<const half_t*>(zeros);
+    c.n = n; c.h = h; c.w_ = wd; c.cin = cin; c.cout = cout; c.k = 3; c.stride = 1; c.pad = 1; c.dil = 1; c.act = act;
+    c.ho = h; c.wo = wd;
+    c.out_fp32 = 0; c.out_img_stride = 0; c.out_base = 0;
+    c.xq = xcd_images_per_group(n);
+    PwArgs a = conv_to_pw(c);
+    a.pool_out = reinterpret_cast<half_t*>(pool_out);
+    int rc = launch_conv_pool(a, reinterpret_cast<hipStream_t>(stream));
+    if (rc) return rc;
+    DN_HIP_CHECK(hipGetLastError());
+    return DN_OK;
+}
+
+// launch_stem on its own: image [n][3][h][w] fp32 in [0, 1], w [27][cout] fp32 (tap (c 3 + ky) 3 + kx), 3 x 3, out [n][ho][wo][cout] fp16. split_ok and
+// scale_log2 are what dn_create derives from the host copy of the weights (check_stems): finite values, the largest magnitude times 2^scale_log2 in [2^14, 2^15)
+extern "C" __attribute__((visibility("default"))) int dn_debug_stem(const float* img, const float* w, const float* bias, void* out, int n, int h, int wd, int cout,
+                                                                   int stride, int pad, int act, const float* mean3, const float* std3, int split_ok, int scale_log2,
+                                                                   void* stream) {
+    DN_REQUIRE(img && w && bias && out && mean3 && std3, "dn_debug_stem: null argument");
+    DN_REQUIRE(n > 0 && h > 0 && wd > 0 && stride >= 1 && pad >= 0 && dn_rows_fit(n, (long)h * wd), "dn_debug_stem: bad geometry, or 2^31 rows or more");
+    StemArgs a{};
+    a.img = img; a.w = w; a.bias = bias; a.out = reinterpret_cast<half_t*>(out);
+    a.n = n; a.h = h; a.w_ = wd; a.cout = cout; a.k = 3; a.stride = stride; a.pad = pad; a.act = act;
+    a.ho = (h + 2 * pad - 3) / stride + 1; a.wo = (wd + 2 * pad - 3) / stride + 1;
+    DN_REQUIRE(a.ho > 0 && a.wo > 0, "dn_debug_stem: empty output");
+    for (int q = 0; q < 3; ++q) { DN_REQUIRE(std3[q] > 0.f, "dn_debug_stem: std must be positive"); a.mean[q] = mean3[q]; a.inv_std[q] = 1.0f / std3[q]; }
+    a.xq = xcd_images_per_group(n);
+    a.split_ok = split_ok ? 1 : 0;
+    a.w_scale = std::ldexp(1.0f, scale_log2);
+    a.w_unscale = std::ldexp(1.0f, -scale_log2);
+    int rc = launch_stem(a, reinterpret_cast<hipStream_t>(stream));
+    if (rc) return rc;
+    DN_HIP_CHECK(hipGetLastError());
+    return DN_OK;
+}
+
+static const char* pw_choice_name(PwChoice::Kernel k) {
+    switch (k) {
+        case PwChoice::NONE: return "none";
+        case PwChoice::AS_POINTWISE: return "as_pointwise";
+        case PwChoice::PW_WSTAT: return "pw_wstat_kernel";
+        case PwChoice::PW_STREAM: return "pw_stream_kernel";
+        case PwChoice::PW_DIRECT: return "pw_direct_kernel";
+        case PwChoice::PW_XS: return "pw_xs_kernel";
+        case PwChoice::PW_TILE: return "pw_kernel";
+        case PwChoice::PW_GROUP: return "pw_group_kernel";
+        case PwChoice::CONV_PATCH: return "conv_patch_kernel";
+        case PwChoice::CONV_PATCH_RESIDENT: return "conv_patch_resident_kernel";
+        case PwChoice::CONV_HALO: return "conv_halo_kernel";
+        case PwChoice::CONV_GLDS: return "conv_glds_kernel";
+    }
+    return "?";
+}
+static int pw_choice_text(const PwChoice& c, char* buf, int capacity) {
+    snprintf(buf, (size_t)capacity, "kernel=%s tile=%dx%d bk=%d pf=%d conv=%d sef=%d fk=%d k=%d t=%d halo=%d head=%d pool=%d", pw_choice_name(c.kernel), c.bp, c.bc,
+             c.bk, c.pf, (int)c.conv, (int)c.sef, (int)c.fk, c.k, c.t, c.halo, (int)c.head, (int)c.pool);
+    return DN_OK;
+}
+
+void depthwise_debug_limits(const DwArgs& a, int tw, bool* in_range, size_t* wlds_bytes);       // depthwise.hip
+
+// family and dims (every entry an int64; pointers are asked for as 0 / 1 flags and stand in as dummies: no function called here reads through one):
+//   "pw"        m cin cout hw act out_fp32 se residual wfrag                    -> pw_choose
+//   "pw_group"  conv count, then count x (m cin cout hw)                        -> pw_group_choose (problems without scale or activation)
+//   "conv"      n h w cin cout k stride pad dil act zeros use[0 plain, 1 pooled, 2 head] cout_b   -> conv_choose; a 1x1 that the pointwise family serves: pw_choose's answer
+//   "dw"        n h w c k stride pad                                            -> dw_choose, dw_fill (range=), dw_wlds_bytes (wlds=)
+//   "stem"      n h w cout stride pad act split_ok                              -> stem_choose
+//   "headfuse"  n H W C nc0 nc1 stride0 stride1                                 -> head_fused_level_supported (supported=)
+//   "headpost"  n H W aloc K A                                                  -> head_fused_post_supported of one level with the epilogue (supported=)
+//   "patch_blocks" n h w                                                        -> conv_patch_resident_blocks (blocks=, launched=: below the launcher's 2^30)
+extern "C" __attribute__((visibility("default"))) int dn_debug_choice(const char* family, const int64_t* d, int nd, char* buf, int capacity) {
+    DN_REQUIRE(family && d && buf && capacity > 0, "dn_debug_choice: null argument");
+    static const half_t dummy_h[8] = {};
+    static const float dummy_f[4] = {};
+    static float dummy_out[4];
+    auto fits = [](int64_t v) { return v >= 0 && v < (1LL << 31); };
+    const std::string f(family);
+    if (f == "pw") {
+        DN_REQUIRE(nd == 9 && fits(d[0]) && d[3] > 0, "dn_debug_choice: pw takes m cin cout hw act out_fp32 se residual wfrag, m below 2^31");
+        PwArgs a{};
+        a.x = a.w = dummy_h; a.bias = dummy_f; a.out = dummy_out;
+        a.m = (int)d[0]; a.cin = (int)d[1]; a.cout = (int)d[2]; a.hw = (int)d[3]; a.act = (int)d[4]; a.out_fp32 = (int)d[5];
+        a.se = d[6] ? dummy_f : nullptr; a.residual = d[7] ? dummy_h : nullptr; a.wfrag = d[8] ? dummy_h : nullptr;
+        return pw_choice_text(pw_choose(a), buf, capacity);
+    }
+    if (f == "pw_group") {
+        DN_REQUIRE(nd >= 2 && d[1] >= 1 && d[1] <= 12 && nd == 2 + 4 * d[1], "dn_debug_choice: pw_group takes conv count and count x (m cin cout hw)");
+        PwArgs arr[12];
+        for (int i = 0; i < (int)d[1]; ++i) {
+            const int64_t* q = d + 2 + 4 * i;
+            DN_REQUIRE(fits(q[0]) && q[3] > 0, "dn_debug_choice: pw_group problem %d: m must lie below 2^31", i);
+            PwArgs a{};
+            a.x = a.w = dummy_h; a.bias = dummy_f; a.out = dummy_out;
+            a.m = (int)q[0]; a.cin = (int)q[1]; a.cout = (int)q[2]; a.hw = (int)q[3]; a.out_fp32 = 1;
+            if (d[0]) { a.cv_k = 3; a.cv_cin = a.cin; a.cin = 9 * a.cv_cin; }
+            arr[i] = a;
+        }
+        return pw_choice_text(pw_group_choose(arr, (int)d[1], d[0] != 0), buf, capacity);
+    }
+    if (f == "conv") {
+        DN_REQUIRE(nd == 13 && d[0] > 0 && d[1] > 0 && d[2] > 0 && d[5] >= 1 && d[6] >= 1 && d[8] >= 1, "dn_debug_choice: conv takes n h w cin cout k stride pad dil act zeros use cout_b");
+        ConvArgs c;
+        c.x = c.w = dummy_h; c.bias = dummy_f; c.out = dummy_out; c.zeros = d[10] ? dummy_h : nullptr;
+        c.n = (int)d[0]; c.h = (int)d[1]; c.w_ = (int)d[2]; c.cin = (int)d[3]; c.cout = (int)d[4]; c.k = (int)d[5]; c.stride = (int)d[6]; c.pad = (int)d[7];
+        c.dil = (int)d[8]; c.act = (int)d[9];
+        c.ho = (c.h + 2 * c.pad - c.dil * (c.k - 1) - 1) / c.stride + 1;
+        c.wo = (c.w_ + 2 * c.pad - c.dil * (c.k - 1) - 1) / c.stride + 1;
+        DN_REQUIRE(c.ho > 0 && c.wo > 0 && dn_rows_fit(d[0], (long)c.ho * c.wo), "dn_debug_choice: conv with an empty output, or 2^31 rows or more");
+        const int use = (int)d[11];
+        c.out_fp32 = use == 2; c.out_img_stride = use == 2 ? (long)c.ho * c.wo * (c.cout + d[12]) : 0; c.out_base = 0; c.xq = 0;
+        PwArgs a = conv_to_pw(c);
+        if (use == 1) a.pool_out = const_cast<half_t*>(dummy_h);
+        if (use == 2 && d[12] > 0) { a.w_b = dummy_h; a.bias_b = dummy_f; a.out_b = dummy_out; a.cout_b = (int)d[12]; }
+        PwChoice ch = conv_choose(a, use == 1 ? CONV_POOLED : use == 2 ? CONV_HEAD : CONV_PLAIN);
+        if (ch.kernel == PwChoice::AS_POINTWISE) ch = pw_choose(conv_1x1_as_pw(a));
+        return pw_choice_text(ch, buf, capacity);
+    }
+    if (f == "dw") {
+        DN_REQUIRE(nd == 7 && d[0] > 0 && d[1] > 0 && d[2] > 0 && d[5] >= 1, "dn_debug_choice: dw takes n h w c k stride pad");
+        DwArgs a{};
+        a.x = a.w = dummy_h; a.bias = dummy_f;
+        a.n = (int)d[0]; a.h = (int)d[1]; a.w_ = (int)d[2]; a.c = (int)d[3]; a.k = (int)d[4]; a.stride = (int)d[5]; a.pad = (int)d[6];
+        a.ho = (a.h + 2 * a.pad - a.k) / a.stride + 1; a.wo = (a.w_ + 2 * a.pad - a.k) / a.stride + 1;
+        const DwChoice c = dw_choose(a);
+        if (c.kernel == DwChoice::NONE) { snprintf(buf, (size_t)capacity, "kernel=none"); return DN_OK; }
+        bool in_range = false;
+        size_t wlds = 0;
+        depthwise_debug_limits(a, c.tw, &in_range, &wlds);
+        snprintf(buf, (size_t)capacity, "kernel=dw_kernel<%d,%d,%d> range=%d wlds=%zu", c.k, c.stride, c.tw, (int)in_range, wlds);
+        return DN_OK;
+    }
+    if (f == "stem") {
+        DN_REQUIRE(nd == 8 && d[0] > 0 && d[1] > 0 && d[2] > 0 && d[4] >= 1, "dn_debug_choice: stem takes n h w cout stride pad act split_ok");
+        StemArgs a{};
+        a.n = (int)d[0]; a.h = (int)d[1]; a.w_ = (int)d[2]; a.cout = (int)d[3]; a.k = 3; a.stride = (int)d[4]; a.pad = (int)d[5]; a.act = (int)d[6]; a.split_ok = (int)d[7];
+        a.ho = (a.h + 2 * a.pad - 3) / a.stride + 1; a.wo = (a.w_ + 2 * a.pad - 3) / a.stride + 1;
+        const StemChoice c = stem_choose(a);
+        static const char* const names[] = {"none", "stem_split_kernel", "stem3s2_kernel", "stem_mfma64p_kernel", "stem_mfma64_kernel", "stem_kernel"};
+        snprintf(buf, (size_t)capacity, "kernel=%s tpw=%d ahead=%d touch=%d", names[c.kernel], c.tpw, c.ahead, (int)c.touch);
+        return DN_OK;
+    }
+    if (f == "headfuse") {
+        DN_REQUIRE(nd == 8 && d[0] > 0, "dn_debug_choice: headfuse takes n H W C nc0 nc1 stride0 stride1");
+        HeadFuseLevel l{};
+        l.x = l.wdg = dummy_h; l.wslot = reinterpret_cast<const unsigned char*>(dummy_h);
+        for (int h = 0; h < 2; ++h) { l.wf[h] = dummy_h; l.bias[h] = dummy_f; l.out[h] = nullptr; l.out_img_stride[h] = (long)d[6 + h]; l.out_base[h] = 0; l.nc[h] = (int)d[4 + h]; }
+        l.n = (int)d[0]; l.H = (int)d[1]; l.W = (int)d[2]; l.C = (int)d[3]; l.act = DN_ACT_RELU6;
+        snprintf(buf, (size_t)capacity, "supported=%d", (int)head_fused_level_supported(l));
+        return DN_OK;
+    }
+    if (f == "headpost") {
+        DN_REQUIRE(nd == 6 && d[0] > 0, "dn_debug_choice: headpost takes n H W aloc K A");
+        HeadFuseLevel l{};
+        l.n = (int)d[0]; l.H = (int)d[1]; l.W = (int)d[2]; l.aloc = (int)d[3]; l.nc[0] = (int)(d[3] * d[4]); l.nc[1] = (int)(4 * d[3]); l.sm = 1; l.sbase = 0;
+        HeadPost post;
+        post.scoresT = dummy_out; post.boxes = reinterpret_cast<float4*>(dummy_out); post.hrows = reinterpret_cast<unsigned*>(dummy_out); post.anchors = dummy_f;
+        post.K = (int)d[4]; post.A = (int)d[5]; post.nb = 1; post.rows_per_image = hist_rows_slots(l.H * l.W);
+        snprintf(buf, (size_t)capacity, "supported=%d", (int)head_fused_post_supported(&l, 1, post));
+        return DN_OK;
+    }
+    if (f == "patch_blocks") {
+        DN_REQUIRE(nd == 3 && d[0] > 0 && d[1] > 0 && d[2] > 0, "dn_debug_choice: patch_blocks takes n h w");
+        const long blocks = conv_patch_resident_blocks((int)d[0], (int)d[1], (int)d[2]);
+        snprintf(buf, (size_t)capacity, "blocks=%ld launched=%d", blocks, (int)(blocks < (1L << 30)));
+        return DN_OK;
+    }
+    dn_set_error("dn_debug_choice: unknown family '%s'", family);
+    return DN_E_INVALID;
 }

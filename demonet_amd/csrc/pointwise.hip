@@ -976,6 +976,7 @@ int launch_pointwise(const PwArgs& a, hipStream_t s) {
     DN_REQUIRE(a.cin % 8 == 0, "pointwise: cin=%d must be a multiple of 8", a.cin);
     DN_REQUIRE(a.out_fp32 || a.cout % 4 == 0, "pointwise: fp16 cout=%d must be a multiple of 4", a.cout);
     DN_REQUIRE(a.m > 0 && a.hw > 0, "pointwise: empty problem");
+    DN_REQUIRE((long)a.m + (a.xq > 0 ? 7L * a.hw : 0L) < (1L << 31), "pointwise: %d rows in images of %d are 2^31 rows or more (int row indices; the XCD grouping rounds the batch up to 8 groups)", a.m, a.hw);
     PwChoice c = pw_choose(a);
     pw_forced(a, false, c);
     if (const int rc = pw_check_honoured(a, c, "pointwise")) return rc;
@@ -1007,6 +1008,7 @@ PwArgs conv_to_pw(const ConvArgs& c) {
 int launch_conv(const ConvArgs& c, hipStream_t s) {
     DN_REQUIRE(c.cin % 32 == 0, "conv: cin=%d must be a multiple of 32 (implicit-GEMM K stage within one tap)", c.cin);
     DN_REQUIRE(c.out_fp32 || c.cout % 4 == 0, "conv: fp16 cout=%d must be a multiple of 4", c.cout);
+    DN_REQUIRE(dn_rows_fit(c.n, (long)c.ho * c.wo), "conv: %d images of %d x %d outputs are 2^31 rows or more (int row indices; the XCD grouping rounds the batch up to 8 groups)", c.n, c.ho, c.wo);
     const PwArgs a = conv_to_pw(c);
     DN_REQUIRE(a.m > 0, "conv: empty problem");
     PwChoice ch = conv_choose(a, CONV_PLAIN);

@@ -47,8 +47,8 @@ def test_library_exports_nothing_the_headers_do_not_declare():
     dbg = open(os.path.join(ROOT, "include", "demonet_hip_debug.h")).read()
     declared = set(_declared_symbols()) | set(re.findall(r"DN_API\s+[\w\s\*]+?\b(dn_\w+)\s*\(", dbg))
     assert set(exported) == declared, sorted(set(exported) ^ declared)
-    assert sorted(s for s in exported if s.startswith("dn_debug_")) == ["dn_debug_clear_graphs", "dn_debug_head_fused_launches", "dn_debug_head_softmax_launches",
-                                                                              "dn_debug_network_input"]
+    assert sorted(s for s in exported if s.startswith("dn_debug_")) == ["dn_debug_choice", "dn_debug_clear_graphs", "dn_debug_conv_pool", "dn_debug_head_fused_launches",
+                                                                              "dn_debug_head_softmax_launches", "dn_debug_last_kernel", "dn_debug_network_input", "dn_debug_stem"]
 
 
 def test_struct_layout_matches_c(tmp_path):
