@@ -13,6 +13,7 @@ DN_MERGE = dict(iou=0, ios=1)
 DN_FRAME = dict(nv12=0, i420=1, rgb24=2, bgr24=3)
 DN_COLOR = dict(bt601=0, bt709=1)
 DN_COLOR_FULL_RANGE = 0x10
+DN_REGION_HFLIP = 1
 DN_SGD_CHUNK = 2048
 DN_SGD_MAX_GATE = 8
 
@@ -42,6 +43,11 @@ class SgdHyper(C.Structure):
 
 class Frame(C.Structure):
     _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_int32 * 3), ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Region(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
 
 
 class TrackParams(C.Structure):
@@ -74,6 +80,8 @@ _SIGNATURES = {
                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dn_forward_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dn_forward_regions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dn_forward_heads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dn_head_outputs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "dn_tensor_ptr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),

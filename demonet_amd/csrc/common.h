@@ -310,6 +310,9 @@ int launch_u8hwc_to_planar(const unsigned char* in, float* out, float* scale_xy,
 // dn_forward_frames: the record table is read on the device; DN_E_UNSUPPORTED for codes dn_frame_codes_known refuses
 bool dn_frame_codes_known(int format, int color);
 int launch_frames_to_planar(const dn_frame* frames, int format, int color, float* out, float* scale_xy, int n, int oh, int ow, hipStream_t s);
+// dn_forward_regions: image i is the rectangle regions[i] of frames[regions[i].frame], both tables read on the device
+int launch_regions_to_planar(const dn_frame* frames, const dn_region* regions, int format, int color, float* out, float* scale_xy, int n, int oh,
+                             int ow, hipStream_t s);
 int launch_resize_bilinear(const float* in, float* out, float* scale_xy, int n, int h, int w, int oh, int ow, hipStream_t s);
 
 // run of tiny layers (<= 32 output pixels each) executed by one workgroup per image with the activations in LDS (tail.hip)

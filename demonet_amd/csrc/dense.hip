@@ -197,6 +197,54 @@ __global__ __launch_bounds__(256) void frames_kernel(const dn_frame* __restrict_
         out[(((size_t)img * 3 + c) * oh + oy) * ow + ox] = bilerp(a[c], b[c], cc[c], d[c], hx, lx, hy, ly);
 }
 
+// Regions of video surfaces (dn_forward_regions): network image i is the rectangle regions[i] of frames[regions[i].frame], mirrored left-right
+// when flagged. frames_kernel's arithmetic in REGION coordinates (the second tap clamps at the region's edge); a tap at region pixel (xr, yr)
+// reads frame pixel (r.x0 + (flip ? w - 1 - xr : xr), r.y0 + yr) through frame_tap, so chroma is sampled in frame coordinates. A region of
+// exactly the network size has sy = oy, sx = ox and weights (1, 0): bilerp returns its first tap unchanged (1 * a + 0 * b = a for the
+// finite, non-negative taps), so that case reads one tap -- the tiles of sliced inference at the default tile size.
+template <int FMT>
+__global__ __launch_bounds__(256) void frame_regions_kernel(const dn_frame* __restrict__ frames, const dn_region* __restrict__ regions,
+                                                            float* __restrict__ out, float* __restrict__ scale_xy, int n, int oh, int ow, FrameColor k) {
+    long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const int ox = (int)(idx % ow);
+    idx /= ow;
+    const int oy = (int)(idx % oh);
+    const long img = idx / oh;
+    if (img >= n) return;
+    const dn_region r = regions[img];
+    const dn_frame f = frames[r.frame];
+    const int h = r.height, w = r.width;
+    const bool flip = (r.flags & DN_REGION_HFLIP) != 0;
+    if (ox == 0 && oy == 0) {
+        scale_xy[2 * img] = (float)w / (float)ow;
+        scale_xy[2 * img + 1] = (float)h / (float)oh;
+    }
+    float* o = out + ((size_t)img * 3 * oh + oy) * ow + ox;
+    const size_t plane = (size_t)oh * ow;
+    if (h == oh && w == ow) {
+        float a[3];
+        frame_tap<FMT>(f, r.x0 + (flip ? w - 1 - ox : ox), r.y0 + oy, k, a);
+        o[0] = a[0]; o[plane] = a[1]; o[2 * plane] = a[2];
+        return;
+    }
+    const float rh = (float)h / (float)oh, rw = (float)w / (float)ow;
+    const float sy = fmaxf(rh * ((float)oy + 0.5f) - 0.5f, 0.f);
+    const float sx = fmaxf(rw * ((float)ox + 0.5f) - 0.5f, 0.f);
+    const int y0 = (int)sy, x0 = (int)sx;
+    const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
+    const float ly = fminf(fmaxf(sy - (float)y0, 0.f), 1.f), lx = fminf(fmaxf(sx - (float)x0, 0.f), 1.f);
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    const int X0 = r.x0 + (flip ? w - 1 - x0 : x0), X1 = r.x0 + (flip ? w - 1 - x1 : x1);
+    const int Y0 = r.y0 + y0, Y1 = r.y0 + y1;
+    float a[3], b[3], cc[3], d[3];
+    frame_tap<FMT>(f, X0, Y0, k, a);
+    frame_tap<FMT>(f, X1, Y0, k, b);
+    frame_tap<FMT>(f, X0, Y1, k, cc);
+    frame_tap<FMT>(f, X1, Y1, k, d);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c * plane] = bilerp(a[c], b[c], cc[c], d[c], hx, lx, hy, ly);
+}
+
 // round(c * 2^14) of cy = 255/219, crv = 2(1 - Kr) cs, cbu = 2(1 - Kb) cs, cgu = 2 Kb (1 - Kb) / Kg cs, cgv = 2 Kr (1 - Kr) / Kg cs with
 // cs = 255/224, yo = 16 (limited range) or cy = cs = 1, yo = 0 (full range); BT.601: Kr, Kb = 0.299, 0.114, BT.709: 0.2126, 0.0722
 // (tests/frames_ref.py derives the same integers from Kr, Kb in float64)
@@ -259,6 +307,25 @@ int launch_frames_to_planar(const dn_frame* frames, int format, int color, float
         case DN_FRAME_I420: hipLaunchKernelGGL(frames_kernel<DN_FRAME_I420>, grid, block, 0, s, frames, out, scale_xy, n, oh, ow, k); break;
         case DN_FRAME_RGB24: hipLaunchKernelGGL(frames_kernel<DN_FRAME_RGB24>, grid, block, 0, s, frames, out, scale_xy, n, oh, ow, k); break;
         default: hipLaunchKernelGGL(frames_kernel<DN_FRAME_BGR24>, grid, block, 0, s, frames, out, scale_xy, n, oh, ow, k); break;
+    }
+    return DN_OK;
+}
+
+int launch_regions_to_planar(const dn_frame* frames, const dn_region* regions, int format, int color, float* out, float* scale_xy, int n, int oh,
+                             int ow, hipStream_t s) {
+    FrameColor k;
+    if (!dn_frame_codes_known(format, color) || !frame_color(color, &k)) {
+        dn_set_error("regions: unknown format %d or colour code 0x%x", format, color);
+        return DN_E_UNSUPPORTED;
+    }
+    const long threads = (long)n * oh * ow;
+    const dim3 grid(dn_cdiv(threads, 256)), block(256);
+    dn_note_kernel("frame_regions_kernel<%d>", format);
+    switch (format) {
+        case DN_FRAME_NV12: hipLaunchKernelGGL(frame_regions_kernel<DN_FRAME_NV12>, grid, block, 0, s, frames, regions, out, scale_xy, n, oh, ow, k); break;
+        case DN_FRAME_I420: hipLaunchKernelGGL(frame_regions_kernel<DN_FRAME_I420>, grid, block, 0, s, frames, regions, out, scale_xy, n, oh, ow, k); break;
+        case DN_FRAME_RGB24: hipLaunchKernelGGL(frame_regions_kernel<DN_FRAME_RGB24>, grid, block, 0, s, frames, regions, out, scale_xy, n, oh, ow, k); break;
+        default: hipLaunchKernelGGL(frame_regions_kernel<DN_FRAME_BGR24>, grid, block, 0, s, frames, regions, out, scale_xy, n, oh, ow, k); break;
     }
     return DN_OK;
 }

@@ -85,13 +85,15 @@ struct Call {
     bool features_only = false;     // dn_forward_features: stop in front of the head launches (implies heads_only)
     const dn_frame* frames = nullptr;   // dn_forward_frames: [n] records in DEVICE memory (images is null, h = w = 0: every record has its own size)
     int format = 0, color = 0;          //   DN_FRAME_*, DN_COLOR_*
+    const dn_region* regions = nullptr; // dn_forward_regions: [n] records in DEVICE memory, image i = a rectangle of frames[regions[i].frame]
     // the call of sub-batch chain k of S (D = detections_per_img): the one place that knows the per-image strides of its arrays
     Call chain(int S, int k, size_t D) const {
         size_t n0 = 0;
         for (int q = 0; q < k; ++q) n0 += sub_count(n, S, q);
         Call c = *this;
         c.n = sub_count(n, S, k);
-        if (frames) c.frames = frames + n0;
+        if (regions) c.regions = regions + n0;      // (the regions name their frames by index: every chain reads the same frame table)
+        else if (frames) c.frames = frames + n0;
         else c.images = static_cast<const char*>(images) + n0 * 3 * (size_t)h * w * (u8 ? 1 : sizeof(float));
         if (!heads_only) { c.boxes += n0 * D * 4; c.scores += n0 * D; c.labels += n0 * D; c.counts += n0; }     // (all four are set: forward_impl)
         if (packed) c.packed += n0 * (D + 1) * 6;
@@ -104,7 +106,7 @@ struct GraphKey {
     int chain;          // sub-batch chain index (one single-chain graph per sub-batch), -1: the whole forward in one graph
     auto fields() const {
         return std::make_tuple(c.images, c.n, c.h, c.w, c.ws, c.boxes, c.scores, c.labels, c.counts, (c.heads_only ? 1 : 0) | (c.u8 ? 2 : 0) | (c.features_only ? 4 : 0), c.packed, chain,
-                               static_cast<const void*>(c.frames), c.format, c.color);
+                               static_cast<const void*>(c.frames), c.format, c.color, static_cast<const void*>(c.regions));
     }
     bool operator<(const GraphKey& o) const { return fields() < o.fields(); }
 };
@@ -1177,7 +1179,14 @@ static int enqueue(dn_plan* p, const Call& call, const Layout& L, hipStream_t s,
     const float* net_in = static_cast<const float*>(call.images);
     const bool resize = (h != d.image_h || w != d.image_w);
     float* scale_xy = nullptr;
-    if (call.frames) {
+    if (call.regions) {
+        // regions of video surfaces: frames_kernel's pass in region coordinates, one record per network image (the ratio block always)
+        float* rz = reinterpret_cast<float*>(ws + L.resized_off);
+        scale_xy = reinterpret_cast<float*>(ws + L.scale_off);
+        int rc = launch_regions_to_planar(call.frames, call.regions, call.format, call.color, rz, scale_xy, n, d.image_h, d.image_w, s);
+        if (rc) return rc;
+        net_in = rz;
+    } else if (call.frames) {
         // video surfaces: colour conversion of the four taps, /255, bilinear resize and the planar layout in one pass; the ratio block is written
         // always (every record has its own size; a ratio of exactly 1 leaves the boxes as they are)
         float* rz = reinterpret_cast<float*>(ws + L.resized_off);
@@ -1298,7 +1307,7 @@ static int capture(dn_plan* p, const Call& call, int S, int chain, hipGraphExec_
 
 static int forward_impl(dn_plan* p, const void* images, int n, int h, int w, float* boxes, float* scores, int64_t* labels,
                         int32_t* counts, void* workspace, size_t ws_bytes, void* stream, bool heads_only, bool u8 = false, bool features_only = false,
-                        const dn_frame* frames = nullptr, int format = 0, int color = 0) {
+                        const dn_frame* frames = nullptr, int format = 0, int color = 0, const dn_region* regions = nullptr) {
     DN_REQUIRE(p && (images || frames) && workspace, "dn_forward: null argument");
     DN_REQUIRE(n > 0 && (frames || (h > 0 && w > 0)), "dn_forward: bad shape n=%d h=%d w=%d", n, h, w);
     struct Busy {
@@ -1323,7 +1332,7 @@ static int forward_impl(dn_plan* p, const void* images, int n, int h, int w, flo
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // (inside the guard: dn_set_packed_output refuses to change the stored setting while a call is in progress)
     DN_REQUIRE(!features_only || !p->profiling, "dn_forward_features: not available between dn_profile_begin and dn_profile_end");
-    const Call call{images, u8, n, h, w, boxes, scores, labels, counts, p->packed_out, reinterpret_cast<unsigned char*>(workspace), heads_only, features_only, frames, format, color};
+    const Call call{images, u8, n, h, w, boxes, scores, labels, counts, p->packed_out, reinterpret_cast<unsigned char*>(workspace), heads_only, features_only, frames, format, color, regions};
     p->heads_partial[workspace] = !heads_only || features_only;      // true: the head arrays of this workspace are not (all) written
     const int S = batch_split(p, n);
     if (p->profiling) {
@@ -1418,6 +1427,20 @@ extern "C" int dn_forward_frames(dn_plan* plan, const dn_frame* frames_dev, int 
     }
     return forward_impl(plan, nullptr, n, 0, 0, boxes_dev, scores_dev, labels_dev, counts_dev, workspace_dev, workspace_bytes, stream,
                         false, false, false, frames_dev, format, color);
+}
+
+extern "C" int dn_forward_regions(dn_plan* plan, const dn_frame* frames_dev, const dn_region* regions_dev, int n, int format, int color,
+                                  float* boxes_dev, float* scores_dev, int64_t* labels_dev, int32_t* counts_dev, void* workspace_dev, size_t workspace_bytes,
+                                  void* stream) {
+    DN_REQUIRE(plan, "dn_forward_regions: null plan");
+    DN_REQUIRE(frames_dev && regions_dev, "dn_forward_regions: null record table");
+    DN_REQUIRE(n > 0, "dn_forward_regions: n=%d", n);
+    if (!dn_frame_codes_known(format, color)) {
+        dn_set_error("dn_forward_regions: unknown format %d or colour code 0x%x", format, color);
+        return DN_E_UNSUPPORTED;
+    }
+    return forward_impl(plan, nullptr, n, 0, 0, boxes_dev, scores_dev, labels_dev, counts_dev, workspace_dev, workspace_bytes, stream,
+                        false, false, false, frames_dev, format, color, regions_dev);
 }
 
 extern "C" int dn_forward_heads(dn_plan* plan, const float* images_dev, int n, int h, int w, void* workspace_dev,

@@ -12,6 +12,14 @@ input -- no converted frame, no stacked block, and frames of different sizes in 
 
 The library trusts the records (it cannot inspect a device table), so `set` validates every plane on the host first: dtype, device, the
 shapes against the frame's width and height, pitch >= payload, and that the plane's last byte lies inside the tensor's storage.
+
+A `RegionTable` names rectangles of those frames, optionally mirrored, as the network's images (dn_region): `SSD.forward_regions`
+runs the forward on them -- the tiles of sliced inference and the passes of flip TTA without a converted frame (sliced.FrameSlicer,
+SSD.detect_sliced_frames, SSD.detect_tta_frames). Every region is validated against its frame's size before its record goes up, and a
+forward refuses a table whose frames have changed size since.
+
+    table = RegionTable(3, "cuda:0").set([(0, 0, 0, 320, 320), (0, 240, 0, 320, 320), (1, 0, 0, 1920, 1080, True)], batch.sizes)
+    boxes, scores, labels, counts = model.forward_regions(batch, table)        # boxes in each region's own coordinates
 """
 import ctypes as C
 from typing import List, Sequence, Tuple
@@ -197,3 +205,118 @@ def track_frames(model, batch: FrameBatch, tracker):
         raise ValueError("track_frames: tracker must be a ByteTracker, got {}".format(type(tracker)))
     boxes, scores, labels, counts = forward_frames(model, batch)
     return tracker.update(boxes, scores, labels, counts)
+
+
+# ---------------------------------------------------------------------------------------------------------------- regions
+def region_records(regions: Sequence, sizes: Sequence[Tuple[int, int]], n: int):
+    """The validated dn_region records of `regions` -- (frame, x0, y0, w, h[, hflip]) tuples -- against sizes[frame] = (height, width), as
+    (a ctypes array of n _lib.Region, the normalised tuples); ValueError naming the region otherwise. Host work only."""
+    if isinstance(regions, Tensor) or not isinstance(regions, (list, tuple)):
+        raise ValueError("expected a list of {} regions, got {}".format(n, type(regions).__name__))
+    if len(regions) != n:
+        raise ValueError("expected {} regions, got {}".format(n, len(regions)))
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    rec = (_lib.Region * n)()
+    norm = []
+    for i, rg in enumerate(regions):
+        if not isinstance(rg, (list, tuple)) or len(rg) not in (5, 6):
+            raise ValueError("region {}: expected (frame, x0, y0, w, h[, hflip]), got {!r}".format(i, rg))
+        vals = rg[:5]
+        if not all(isinstance(v, int) and not isinstance(v, bool) for v in vals):
+            raise ValueError("region {}: frame, x0, y0, w, h must be ints, got {!r}".format(i, tuple(rg)))
+        f, x0, y0, w, h = vals
+        flip = bool(rg[5]) if len(rg) == 6 else False
+        if any(abs(v) > _INT32_MAX for v in vals) or x0 + w > _INT32_MAX or y0 + h > _INT32_MAX:
+            raise ValueError("region {}: {!r} does not fit the record's int32".format(i, tuple(rg)))
+        if f < 0 or f >= len(sizes):
+            raise ValueError("region {}: frame index {} out of range ({} frames)".format(i, f, len(sizes)))
+        H, W = sizes[f]
+        if w < 1 or h < 1:
+            raise ValueError("region {}: bad size {} x {} (width, height >= 1)".format(i, w, h))
+        if x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+            raise ValueError("region {}: the rectangle x {} .. {}, y {} .. {} leaves frame {} of {} x {} (width x height)".format(
+                i, x0, x0 + w, y0, y0 + h, f, W, H))
+        r = rec[i]
+        r.frame, r.x0, r.y0, r.width, r.height, r.flags = f, x0, y0, w, h, _lib.DN_REGION_HFLIP if flip else 0
+        norm.append((f, x0, y0, w, h, flip))
+    return rec, norm
+
+
+class RegionTable:
+    """n regions of the frames of a FrameBatch as one forward's input (SSD.forward_regions); owns the table of n dn_region records in device
+    memory. The table keeps its address for the life of the object, so the forward's captured graph replays on whatever `set` put there last."""
+
+    def __init__(self, n: int, device):
+        if not isinstance(n, int) or n < 1:
+            raise ValueError("n must be a positive int, got {!r}".format(n))
+        self.n = n
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.table = None           # [n * 32] uint8 on the device: allocated by the first set()
+        self.regions: List[Tuple] = []      # (frame, x0, y0, w, h, hflip) per network image
+        self.frame_sizes = {}       # frame index -> the (height, width) its regions were validated against
+        self._host = None
+
+    def set(self, regions: Sequence, sizes: Sequence[Tuple[int, int]]):
+        """Name the table's n regions: (frame, x0, y0, w, h[, hflip]) tuples of ints, validated against sizes[frame] = (height, width) -- pass
+        FrameBatch.sizes. Frame index in range, w, h >= 1, x0, y0 >= 0, x0 + w <= W, y0 + h <= H, everything within int32; ValueError naming the
+        region before anything is changed. The records go up from pinned memory on the current stream; the host does not wait."""
+        rec, norm = region_records(regions, sizes, self.n)
+        if self.device.type != "cuda":
+            raise RuntimeError("demonet_amd runs on an MI355X only (regions must be on a cuda device); there is no CPU fallback path")
+        host = torch.frombuffer(rec, dtype=torch.uint8).pin_memory()
+        if self.table is None:
+            self.table = torch.empty(self.n * C.sizeof(_lib.Region), dtype=torch.uint8, device=self.device)
+        self.table.copy_(host, non_blocking=True)
+        self._host = host
+        self.regions = norm
+        self.frame_sizes = {f: (int(sizes[f][0]), int(sizes[f][1])) for f in sorted({r[0] for r in norm})}
+        return self
+
+
+def check_regions(what: str, model, batch, table):
+    """What every forward over regions checks before a record reaches the device: the objects, one device, both set, and that every frame the
+    regions name has, in the batch AS IT IS NOW, the size the regions were validated against."""
+    if not isinstance(batch, FrameBatch):
+        raise ValueError("{}: expected a FrameBatch, got {}".format(what, type(batch).__name__))
+    if not isinstance(table, RegionTable):
+        raise ValueError("{}: expected a RegionTable, got {}".format(what, type(table).__name__))
+    dev = batch.device
+    mdev = next(model.parameters()).device
+    if mdev != dev:
+        raise ValueError("{}: the FrameBatch is on {}, the model on {}".format(what, dev, mdev))
+    if table.device != dev:
+        raise ValueError("{}: the RegionTable is on {}, the FrameBatch on {}".format(what, table.device, dev))
+    if batch.table is None:
+        raise ValueError("{}: the FrameBatch names no frames yet: call set() first".format(what))
+    if table.table is None:
+        raise ValueError("{}: the RegionTable names no regions yet: call set() first".format(what))
+    for f, size in table.frame_sizes.items():
+        have = batch.sizes[f] if f < len(batch.sizes) else None
+        if have != size:
+            raise ValueError("{}: stale sizes: the regions of frame {} were validated against {} (height, width), the batch now holds {}; "
+                             "set() the table again".format(what, f, size, have if have is not None else "{} frames".format(len(batch.sizes))))
+
+
+def run_regions(model, batch: FrameBatch, regions_ptr: int, n: int, packed=None):
+    """dn_forward_regions on n records at regions_ptr (checked by the caller) -> the model's (n, 0, 0) output tensors"""
+    dev = batch.device
+    handle = model._plan(dev)
+    model._check_packed(packed, n, dev)
+    b = model._buffers_for(n, 0, 0, dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    model._set_packed(packed)
+    model._feat_gen += 1
+    p = C.c_void_p
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dn_forward_regions(p(handle), p(batch.table.data_ptr()), p(regions_ptr), n, batch.format_code, batch.color_code,
+                                                 *(p(t.data_ptr()) for t in b["outs"]), p(b["ws"].data_ptr()), b["ws"].numel(), p(stream)),
+                   "dn_forward_regions")
+    return b["outs"]
+
+
+def forward_regions(model, batch: FrameBatch, table: RegionTable, packed=None):
+    """SSD.forward_regions (see there)."""
+    check_regions("forward_regions", model, batch, table)
+    return run_regions(model, batch, table.table.data_ptr(), table.n, packed)

@@ -144,11 +144,19 @@ def _detect(what: str, model_list, weights, images, hflip: bool, fuse: str, thre
                 sb[where, p + 1] = torch.stack([width - fb[..., 2], fb[..., 1], width - fb[..., 0], fb[..., 3]], -1)      # x1' = W - x2, x2' = W - x1
                 for dst, src in zip((ss, sl, sc), (os_, ol, oc)):
                     dst[where, p + 1] = src[n:]
+    w_dev = None
+    if fuse == "wbf" and weights is not None:
+        w_dev = torch.tensor([w for w in weights for _ in range(2 if hflip else 1)] * G, dtype=torch.float32).to(device)
+    return _reduce(fuse, sb, ss, sl, sc, G, P, D, w_dev, thresh, skip_thresh, device)
+
+
+def _reduce(fuse: str, sb, ss, sl, sc, G: int, P: int, D: int, w_dev, thresh: float, skip_thresh: float, device):
+    """The staged sources [G, P, ...] of G images (sources g * P .. g * P + P - 1 form group g) -> the fused or merged per-image results"""
+    S = G * P
     sb, ss, sl, sc = sb.view(S, D, 4), ss.view(S, D), sl.view(S, D), sc.view(S)
     offsets = torch.zeros((S, 2), dtype=torch.float32, device=device)
     group_begin = list(range(0, S + 1, P))
     if fuse == "wbf":
-        w_dev = None if weights is None else torch.tensor([w for w in weights for _ in range(2 if hflip else 1)] * G, dtype=torch.float32).to(device)
         boxes, scores, labels, counts = fuse_detections(sb, ss, sl, sc, offsets, group_begin, w_dev, thresh, skip_thresh, D)
     else:
         boxes, scores, labels, counts = merge_detections(sb, ss, sl, sc, offsets, group_begin, thresh, "iou", False, D)
@@ -159,6 +167,49 @@ def _detect(what: str, model_list, weights, images, hflip: bool, fuse: str, thre
 def detect_tta(model, images, hflip: bool = True, fuse: str = "wbf", thresh: float = None, skip_thresh: float = None):
     """SSD.detect_tta (see there)."""
     return _detect("detect_tta", [model], None, images, bool(hflip), fuse, thresh, skip_thresh)
+
+
+def detect_tta_frames(model, batch, fuse: str = "wbf", thresh: float = None, skip_thresh: float = None):
+    """SSD.detect_tta_frames (see there)."""
+    from .frames import FrameBatch, RegionTable, forward_regions
+    what = "detect_tta_frames"
+    if fuse not in FUSE_MODES:
+        raise ValueError("{}: fuse must be one of {}, got {!r}".format(what, FUSE_MODES, fuse))
+    if model.training:
+        raise ValueError("{}: the models must be in eval mode".format(what))
+    if not isinstance(batch, FrameBatch):
+        raise ValueError("{}: expected a FrameBatch, got {}".format(what, type(batch).__name__))
+    if batch.table is None:
+        raise ValueError("{}: the FrameBatch names no frames yet: call set() first".format(what))
+    thresh = float(model.nms_thresh if thresh is None else thresh)
+    skip_thresh = float(model.score_thresh if skip_thresh is None else skip_thresh)
+    _check_thresholds(what, thresh, skip_thresh)
+    D, G, device = model.detections_per_img, batch.n, batch.device
+    if fuse == "wbf":
+        check_fuse_limits(2, D, what)
+    # per camera layout: the 2 G regions -- every frame whole, then every frame whole and mirrored -- and the frames' widths for the map-back
+    cache = model.__dict__.setdefault("_tta_tables", {})
+    key = (tuple(batch.sizes), str(device))
+    entry = cache.get(key)
+    if entry is None:
+        regions = [(g, 0, 0, w, h, flip) for flip in (False, True) for g, (h, w) in enumerate(batch.sizes)]
+        if len(cache) >= 4:
+            cache.clear()
+        entry = cache[key] = (RegionTable(2 * G, device).set(regions, batch.sizes),
+                              torch.tensor([float(w) for _, w in batch.sizes], dtype=torch.float32).to(device)[:, None])
+    table, width = entry
+    ob, os_, ol, oc = forward_regions(model, batch, table)       # both passes as one forward of 2 G images
+    sb = torch.empty((G, 2, D, 4), dtype=torch.float32, device=device)
+    ss = torch.empty((G, 2, D), dtype=torch.float32, device=device)
+    sl = torch.empty((G, 2, D), dtype=torch.int64, device=device)
+    sc = torch.empty((G, 2), dtype=torch.int32, device=device)
+    for dst, src in zip((sb, ss, sl, sc), (ob, os_, ol, oc)):
+        dst[:, 0] = src[:G]
+        if dst is not sb:
+            dst[:, 1] = src[G:]
+    fb = ob[G:]
+    sb[:, 1] = torch.stack([width - fb[..., 2], fb[..., 1], width - fb[..., 0], fb[..., 3]], -1)      # x1' = W - x2, x2' = W - x1
+    return _reduce(fuse, sb, ss, sl, sc, G, 2, D, None, thresh, skip_thresh, device)
 
 
 def ensemble_detect(model_list, images, weights: Sequence[float] = None, hflip: bool = False, fuse: str = "wbf", thresh: float = None,

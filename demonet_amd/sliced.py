@@ -8,6 +8,10 @@ between the image and the result there is one device-to-host copy, the merged co
 
 `merge_detections` is the general piece: an NMS over detections that already exist, per class or class-agnostic, for any set of sources with one
 offset each (tiles, flipped passes, several models).
+
+`FrameSlicer` is the same on video surfaces: the tiles and the whole-frame passes are regions of a frames.FrameBatch, read by the
+forward's first kernel, the regions of all frames share forwards, and the merged detections stay padded on the device (no host copy at all),
+ready for ByteTracker.update.
 """
 import ctypes as C
 from typing import List, Sequence, Tuple
@@ -138,6 +142,27 @@ def merge_detections(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tens
     return (ob, os_, ol, oc, src) if return_src else (ob, os_, ol, oc)
 
 
+def _slice_args(what: str, model, tile, merge_thresh, metric, max_tiles_per_forward):
+    """-> (th0, tw0, max_tiles_per_forward, merge threshold) of the arguments detect_sliced and FrameSlicer share; ValueError for a bad one"""
+    if tile is None:
+        tw0, th0 = model.graph.size
+    elif isinstance(tile, int):
+        th0 = tw0 = tile
+    else:
+        th0, tw0 = (int(x) for x in tile)
+    if th0 < 1 or tw0 < 1:
+        raise ValueError("{}: tile must be positive, got {!r}".format(what, tile))
+    if metric not in _lib.DN_MERGE:
+        raise ValueError("{}: metric must be one of {}, got {!r}".format(what, sorted(_lib.DN_MERGE), metric))
+    max_tiles_per_forward = int(max_tiles_per_forward)
+    if max_tiles_per_forward < 1:
+        raise ValueError("{}: max_tiles_per_forward must be >= 1, got {}".format(what, max_tiles_per_forward))
+    thresh = model.nms_thresh if merge_thresh is None else float(merge_thresh)
+    if thresh != thresh:
+        raise ValueError("{}: merge_thresh is NaN".format(what))
+    return th0, tw0, max_tiles_per_forward, thresh
+
+
 def detect_sliced(model, images, tile=None, overlap: float = 0.25, full_image: bool = True, merge_thresh: float = None, metric: str = "iou",
                   class_agnostic: bool = False, max_tiles_per_forward: int = 64):
     """SSD.detect_sliced (see there)."""
@@ -148,22 +173,7 @@ def detect_sliced(model, images, tile=None, overlap: float = 0.25, full_image: b
     if not imgs:
         return []
     _check_images("detect_sliced", imgs)
-    if tile is None:
-        tw0, th0 = model.graph.size
-    elif isinstance(tile, int):
-        th0 = tw0 = tile
-    else:
-        th0, tw0 = (int(x) for x in tile)
-    if th0 < 1 or tw0 < 1:
-        raise ValueError("detect_sliced: tile must be positive, got {!r}".format(tile))
-    if metric not in _lib.DN_MERGE:
-        raise ValueError("detect_sliced: metric must be one of {}, got {!r}".format(sorted(_lib.DN_MERGE), metric))
-    max_tiles_per_forward = int(max_tiles_per_forward)
-    if max_tiles_per_forward < 1:
-        raise ValueError("detect_sliced: max_tiles_per_forward must be >= 1, got {}".format(max_tiles_per_forward))
-    thresh = model.nms_thresh if merge_thresh is None else float(merge_thresh)
-    if thresh != thresh:
-        raise ValueError("detect_sliced: merge_thresh is NaN")
+    th0, tw0, max_tiles_per_forward, thresh = _slice_args("detect_sliced", model, tile, merge_thresh, metric, max_tiles_per_forward)
     D = model.detections_per_img
     grids = [tile_grid(img.shape[1], img.shape[2], th0, tw0, overlap) for img in imgs]      # (ValueError for a bad overlap)
     extra = 1 if full_image else 0
@@ -205,3 +215,121 @@ def detect_sliced(model, images, tile=None, overlap: float = 0.25, full_image: b
     boxes, scores, labels, counts = merge_detections(sb, ss, sl, sc, offsets_dev, group_begin, thresh, metric, class_agnostic, D)
     cnt = counts.tolist()                                # the one device->host copy
     return [{"boxes": boxes[g, :c], "scores": scores[g, :c], "labels": labels[g, :c]} for g, c in enumerate(cnt)]
+
+
+class FrameSlicer:
+    """Sliced inference straight from video surfaces, built once per camera layout: sizes = FrameBatch.sizes, one (height, width) per
+    frame; the other arguments are detect_sliced's. Holds the tile_grid of every frame, the region table (per frame: its tiles in tile_grid's
+    order, then with full_image one whole-frame region), the offsets, group_begin, the staging arrays and the merge workspace.
+
+    slicer(batch) runs ceil(S / max_tiles_per_forward) forwards over ALL S regions of ALL frames (a forward may span frames), merges with one
+    dn_merge_detections and returns padded device tensors (boxes [G, D, 4], scores [G, D], labels [G, D] int64, counts [G] int32), G = frames,
+    in each frame's pixel coordinates: the slicer's own tensors, overwritten by its next call. No device-to-host copy, no host wait.
+
+    Every forward reads its records from ONE slot table of max_tiles_per_forward records, filled by a device-to-device copy on the stream, and
+    writes the model's (n, 0, 0) output buffers, which are then copied into the staging arrays: the plan sees at most two graph keys (the full
+    sub-batch and the remainder), however many sub-batches a step has."""
+
+    def __init__(self, model, sizes, tile=None, overlap: float = 0.25, full_image: bool = True, merge_thresh: float = None, metric: str = "iou",
+                 class_agnostic: bool = False, max_tiles_per_forward: int = 64):
+        what = "FrameSlicer"
+        th0, tw0, self.max_tiles_per_forward, self.thresh = _slice_args(what, model, tile, merge_thresh, metric, max_tiles_per_forward)
+        self.model, self.metric, self.class_agnostic, self.full_image = model, metric, bool(class_agnostic), bool(full_image)
+        self.sizes = [(int(h), int(w)) for h, w in sizes]
+        if not self.sizes:
+            raise ValueError("FrameSlicer: no frame sizes")
+        self.D = D = model.detections_per_img
+        self.grids = [tile_grid(h, w, th0, tw0, overlap) for h, w in self.sizes]        # (ValueError for a bad size or overlap)
+        extra = 1 if self.full_image else 0
+        self.regions, self.offsets, self.group_begin = [], [], [0]
+        for f, ((h, w), (origins, th, tw)) in enumerate(zip(self.sizes, self.grids)):
+            check_merge_limits(len(origins) + extra, D, what)
+            self.regions += [(f, x, y, tw, th, False) for x, y in origins] + [(f, 0, 0, w, h, False)] * extra
+            self.offsets += [(float(x), float(y)) for x, y in origins] + [(0.0, 0.0)] * extra
+            self.group_begin.append(len(self.regions))
+        self.S, self.G = len(self.regions), len(self.sizes)
+        from .frames import region_records
+        region_records(self.regions, self.sizes, self.S)      # (every region lies inside its frame by construction: checked all the same)
+        self.table = None           # the device side: made by the first call
+
+    def _materialise(self, device):
+        from .frames import RegionTable
+        S, G, D, M = self.S, self.G, self.D, min(self.max_tiles_per_forward, self.S)
+        self.table = RegionTable(S, device).set(self.regions, self.sizes)
+        self.slot = torch.zeros(M * C.sizeof(_lib.Region), dtype=torch.uint8, device=device)
+        self.offsets_dev = torch.tensor(self.offsets, dtype=torch.float32).to(device)
+        self.staging = (torch.empty((S, D, 4), dtype=torch.float32, device=device), torch.empty((S, D), dtype=torch.float32, device=device),
+                        torch.empty((S, D), dtype=torch.int64, device=device), torch.empty((S,), dtype=torch.int32, device=device))
+        self.ws = torch.empty(_lib.lib().dn_merge_detections_workspace_bytes(S, D, G), dtype=torch.uint8, device=device)
+        self.outs = _padded_outputs(G, D, device, False)[:4]
+        self._gb = (C.c_int32 * (G + 1))(*self.group_begin)
+
+    def __call__(self, batch):
+        from .frames import FrameBatch, check_regions, run_regions
+        m = self.model
+        if m.training:
+            raise ValueError("FrameSlicer: the model must be in eval mode")
+        if m.detections_per_img != self.D:
+            raise ValueError("FrameSlicer: built for detections_per_img = {}, the model now has {}".format(self.D, m.detections_per_img))
+        if not isinstance(batch, FrameBatch):
+            raise ValueError("FrameSlicer: expected a FrameBatch, got {}".format(type(batch).__name__))
+        if batch.table is None:
+            raise ValueError("FrameSlicer: the FrameBatch names no frames yet: call set() first")
+        if list(batch.sizes) != self.sizes:
+            raise ValueError("FrameSlicer: stale sizes: built for frames of {} (height, width), the batch holds {}".format(self.sizes, list(batch.sizes)))
+        mdev = next(m.parameters()).device
+        if mdev != batch.device:
+            raise ValueError("FrameSlicer: the FrameBatch is on {}, the model on {}".format(batch.device, mdev))
+        if self.table is None:
+            self._materialise(batch.device)
+        check_regions("FrameSlicer", m, batch, self.table)
+        dev, rb, M = batch.device, C.sizeof(_lib.Region), self.max_tiles_per_forward
+        for a in range(0, self.S, M):
+            nb = min(M, self.S - a)
+            self.slot[:nb * rb].copy_(self.table.table[a * rb:(a + nb) * rb])
+            outs = run_regions(m, batch, self.slot.data_ptr(), nb)
+            for dst, src in zip(self.staging, outs):
+                dst[a:a + nb].copy_(src)
+        sb, ss, sl, sc = self.staging
+        ob, os_, ol, oc = self.outs
+        p = C.c_void_p
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().dn_merge_detections(p(sb.data_ptr()), p(ss.data_ptr()), p(sl.data_ptr()), p(sc.data_ptr()), p(self.offsets_dev.data_ptr()),
+                                                      self.S, self.D, self._gb, self.G, _lib.DN_MERGE[self.metric], float(self.thresh),
+                                                      int(self.class_agnostic), self.D, p(ob.data_ptr()), p(os_.data_ptr()), p(ol.data_ptr()),
+                                                      p(oc.data_ptr()), None, p(self.ws.data_ptr()), self.ws.numel(), _stream(dev)), "dn_merge_detections")
+        return self.outs
+
+
+def detect_sliced_frames(model, batch, tile=None, overlap: float = 0.25, full_image: bool = True, merge_thresh: float = None, metric: str = "iou",
+                         class_agnostic: bool = False, max_tiles_per_forward: int = 64):
+    """SSD.detect_sliced_frames (see there)."""
+    from .frames import FrameBatch
+    if not isinstance(batch, FrameBatch):
+        raise ValueError("detect_sliced_frames: expected a FrameBatch, got {}".format(type(batch).__name__))
+    if batch.table is None:
+        raise ValueError("detect_sliced_frames: the FrameBatch names no frames yet: call set() first")
+    key = (tuple(batch.sizes), str(batch.device), tile if tile is None or isinstance(tile, int) else tuple(tile), overlap, bool(full_image), merge_thresh,
+           metric, bool(class_agnostic), int(max_tiles_per_forward), model.detections_per_img, model.nms_thresh)
+    cache = model.__dict__.setdefault("_frame_slicers", {})
+    slicer = cache.get(key)
+    if slicer is None:
+        slicer = FrameSlicer(model, batch.sizes, tile, overlap, full_image, merge_thresh, metric, class_agnostic, max_tiles_per_forward)
+        if len(cache) >= 4:
+            cache.clear()
+        cache[key] = slicer
+    boxes, scores, labels, counts = (t.clone() for t in slicer(batch))      # (the slicer's tensors are overwritten by its next call)
+    cnt = counts.tolist()                                # the one device->host copy
+    return [{"boxes": boxes[g, :c], "scores": scores[g, :c], "labels": labels[g, :c]} for g, c in enumerate(cnt)]
+
+
+def track_sliced_frames(model, batch, tracker, slicer: FrameSlicer):
+    """SSD.track_sliced_frames (see there)."""
+    from .track import ByteTracker, MAX_D as TRACK_MAX_D
+    if not isinstance(tracker, ByteTracker):
+        raise ValueError("track_sliced_frames: tracker must be a ByteTracker, got {}".format(type(tracker)))
+    if not isinstance(slicer, FrameSlicer) or slicer.model is not model:
+        raise ValueError("track_sliced_frames: slicer must be a FrameSlicer of this model")
+    if slicer.D > TRACK_MAX_D:
+        raise ValueError("track_sliced_frames: detections_per_img = {} rows per frame, the tracker takes at most {}".format(slicer.D, TRACK_MAX_D))
+    return tracker.update(*slicer(batch))

@@ -415,6 +415,38 @@ class SSD(_Tracked):
         from .frames import track_frames
         return track_frames(self, batch, tracker)
 
+    def forward_regions(self, batch, table, packed: Optional[Tensor] = None):
+        """The forward on REGIONS of video surfaces (demonet_amd/frames.py): table is a frames.RegionTable of n (frame, x0, y0, w, h[,
+        hflip]) rectangles of the FrameBatch's frames; network image i is rectangle i, mirrored left-right when flagged, resized to the network
+        size by forward_frames' pass in region coordinates (include/demonet_hip.h, dn_forward_regions): bit for bit what forward_uint8 computes
+        from the rectangle cut out of the converted frame. Boxes are in each region's own coordinates (a mirrored region's are the mirrored ones).
+        Returns the padded device tensors of forward_batch. ValueError for an unset batch or table, another device, and STALE SIZES: a frame
+        the regions name whose size in the batch is no longer the one the regions were validated against (set() the table again)."""
+        from .frames import forward_regions
+        return forward_regions(self, batch, table, packed)
+
+    def detect_sliced_frames(self, batch, tile=None, overlap: float = 0.25, full_image: bool = True, merge_thresh: Optional[float] = None,
+                             metric: str = "iou", class_agnostic: bool = False, max_tiles_per_forward: int = 64) -> List[Dict[str, Tensor]]:
+        """detect_sliced on the frames of a FrameBatch, with the same arguments and the same results: the tiles and the whole-frame passes are
+        regions of the surfaces (sliced.FrameSlicer) -- no converted frame, no float image, and the regions of ALL frames share
+        forwards of at most max_tiles_per_forward images. One device-to-host copy, the merged counts. The slicer is cached on (batch.sizes,
+        arguments). Returns one {"boxes", "scores", "labels"} per frame, in frame coordinates."""
+        from .sliced import detect_sliced_frames
+        return detect_sliced_frames(self, batch, tile, overlap, full_image, merge_thresh, metric, class_agnostic, max_tiles_per_forward)
+
+    def detect_tta_frames(self, batch, fuse: str = "wbf", thresh: Optional[float] = None, skip_thresh: Optional[float] = None) -> List[Dict[str, Tensor]]:
+        """detect_tta (hflip=True) on the frames of a FrameBatch: every frame is one plain and one mirrored whole-frame region, all of them in one
+        forward, mapped back and fused or merged as detect_tta does. Returns one {"boxes", "scores", "labels"} per frame."""
+        from .fusion import detect_tta_frames
+        return detect_tta_frames(self, batch, fuse, thresh, skip_thresh)
+
+    def track_sliced_frames(self, batch, tracker, slicer):
+        """Video -> tiles -> merge -> ByteTrack without a host wait per frame step: tracker.update(*slicer(batch)) for a sliced.FrameSlicer of
+        this model (frame g of the batch is the current frame of stream g). Returns what ByteTracker.update returns. ValueError when
+        detections_per_img exceeds the tracker's 512 rows."""
+        from .sliced import track_sliced_frames
+        return track_sliced_frames(self, batch, tracker, slicer)
+
     def batch_split(self, n: int) -> int:
         """Number of parallel sub-batch launch chains a forward of n images is issued as (1 = a single chain)."""
         if self._handle is None:

@@ -135,6 +135,36 @@ DN_API int dn_forward_frames(dn_plan* plan, const dn_frame* frames_dev, int n, i
                       float* boxes_dev, float* scores_dev, int64_t* labels_dev, int32_t* counts_dev,
                       void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The same with REGIONS of video surfaces as input: network image i is a rectangle of one of the frames, optionally mirrored -- the tiles of
+ * sliced inference and the two passes of flip test-time augmentation straight from the surfaces, tiles and whole-frame passes of several
+ * cameras in one forward. frames_dev is a dn_frame table as above (any number of records); regions_dev = [n] records, one per network image.
+ * Arithmetic: with r = regions[i], f = frames[r.frame], h = r.height, w = r.width, the quantities rh, rw, sy, sx, y0, x0, y1, x1, ly, lx are
+ * dn_forward_u8's, expression for expression, IN REGION COORDINATES: the second tap clamps at the region's last row and column
+ * (x0 < w - 1), not the frame's. A tap at region pixel (xr, yr) reads frame pixel X = r.x0 + (HFLIP ? w - 1 - xr : xr), Y = r.y0 + yr, converted
+ * as above -- so its chroma sample is (X >> 1, Y >> 1) in FRAME coordinates -- then /255 and the bilinear weights without contraction. The
+ * ratio of image i is (w / ow, h / oh) of the region. Consequence: the network input of image i equals, bit for bit, what dn_forward_u8
+ * computes from the rectangle cut out of the converted frame (mirrored left-right when flagged); a region (f, 0, 0, W, H, 0) reproduces
+ * dn_forward_frames. A region of exactly the network size has weights (1, 0): the kernel then reads one tap, with the same bits.
+ * Boxes come back in the region's own coordinates; for a mirrored region these are the MIRRORED region's, the caller maps x1' = w - x2,
+ * x2' = w - x1. */
+enum { DN_REGION_HFLIP = 1 };
+typedef struct dn_region {      /* 32 bytes, one per network image, in DEVICE memory */
+    int32_t frame;              /* index into the dn_frame table */
+    int32_t x0, y0, width, height;   /* the rectangle, in that frame's pixels; wholly inside the frame */
+    int32_t flags;              /* 0 or DN_REGION_HFLIP */
+    int32_t reserved[2];        /* 0 */
+} dn_region;
+/* Both tables are read by the first kernel of the forward WHEN IT RUNS: a captured graph is keyed on both addresses (with n, format, color
+ * and the output pointers) and replays on whatever surfaces and rectangles they name at that moment. A forward that runs as several
+ * sub-batch chains advances the REGION table by the chain's first image; every chain indexes the same frame table.
+ * TRUST BOUNDARY: AS FOR dn_frame, THE LIBRARY CANNOT INSPECT A DEVICE TABLE AND TRUSTS BOTH: every region's frame index inside the frame
+ * table, width, height >= 1, x0, y0 >= 0, x0 + width <= that frame's width, y0 + height <= its height; a wrong record is an out-of-bounds
+ * device read. Validate on the host before the records go up (Python: frames.RegionTable.set, SSD.forward_regions).
+ * DN_E_INVALID for a null table or n <= 0, DN_E_UNSUPPORTED for an unknown format or colour code, both before anything is launched. */
+DN_API int dn_forward_regions(dn_plan* plan, const dn_frame* frames_dev, const dn_region* regions_dev, int n, int format, int color,
+                       float* boxes_dev, float* scores_dev, int64_t* labels_dev, int32_t* counts_dev,
+                       void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Backbone + heads only (no post-process). The head outputs live inside the workspace; query them with
  * dn_head_outputs:  cls_logits [n][A][K] fp32, bbox_regression [n][A][4] fp32 (generalized_ssd.py:60-74). Valid after
  * dn_forward_heads only: dn_forward may compute softmax / box decode inside the head launch and then never writes the logits
