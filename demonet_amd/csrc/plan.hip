@@ -1617,6 +1617,31 @@ extern "C" int dn_expand_depthwise(const void* x, const void* w1, const float* b
 
 extern "C" int dn_expand_depthwise_tiles(int ho, int wo, int stride) { return expdw_tiles_per_image(ho, wo, stride); }
 
+extern "C" int dn_depthwise_pointwise(const void* x, const void* wd, const float* bd, const void* w, const float* b, void* out, int n, int h,
+                                      int wdt, int c, int cout, int act_dw, int act, int has_res, void* stream) {
+    DN_REQUIRE(x && wd && bd && w && b && out, "dn_depthwise_pointwise: null argument");
+    DN_REQUIRE(n > 0 && h > 0 && wdt > 0 && c > 0 && cout > 0, "dn_depthwise_pointwise: bad geometry");
+    if (!dn_rows_fit(n, (long)h * wdt)) {
+        dn_set_error("dn_depthwise_pointwise: n=%d images of %d x %d pixels do not fit 32-bit row indices", n, h, wdt);
+        return DN_E_UNSUPPORTED;
+    }
+    DwArgs d{};
+    d.x = reinterpret_cast<const half_t*>(x); d.w = reinterpret_cast<const half_t*>(wd); d.bias = bd;
+    d.n = n; d.h = h; d.w_ = wdt; d.c = c; d.k = 3; d.stride = 1; d.pad = 1; d.act = act_dw; d.ho = h; d.wo = wdt;
+    PwArgs a{};
+    a.x = d.x; a.w = reinterpret_cast<const half_t*>(w); a.bias = b; a.residual = has_res ? d.x : nullptr; a.se = nullptr; a.out = out;
+    a.m = n * h * wdt; a.cin = c; a.cout = cout; a.hw = h * wdt; a.act = act; a.out_fp32 = 0; a.out_img_stride = 0; a.out_base = 0;
+    a.xq = d.xq = xcd_images_per_group(n);
+    if (!pw_dw_direct_supported(a, d)) {
+        dn_set_error("dn_depthwise_pointwise: unsupported n=%d h=%d w=%d c=%d cout=%d has_res=%d", n, h, wdt, c, cout, has_res);
+        return DN_E_UNSUPPORTED;
+    }
+    int rc = launch_pw_dw_direct(a, d, reinterpret_cast<hipStream_t>(stream));
+    if (rc) return rc;
+    DN_HIP_CHECK(hipGetLastError());
+    return DN_OK;
+}
+
 extern "C" int dn_dense_conv(const void* x, const void* w, const float* bias, const void* zeros, void* out, int n, int h, int wd,
                              int cin, int cout, int k, int stride, int pad, int dil, int act, void* stream) {
     DN_REQUIRE(x && w && bias && out, "dn_dense_conv: null argument");

@@ -505,6 +505,204 @@ __global__ __launch_bounds__(256) void pw_dw_direct_kernel(PwDwArgs q, int tiles
     }
 }
 
+// The same launch with its input staged through LDS (DN_PW_DW_LDS, default on; 0 = the body above). Above, a wave asks the L1 for every
+// input line up to ten times (nine taps of neighbouring pixels, then the centre line once more in the accumulator's layout as the residual):
+// 9.5 KB requested for 1 KB of unique input per 32-pixel tile, on 64-bit addresses with a select each, by waves that live for one round trip.
+// Here a workgroup owns a BAND of consecutive pixels of one image in flattened (y, x) order (DN_PW_DW_BAND pixels; the last band of an image
+// is short, no band crosses an image, and the XCD grouping is the launcher's: xcd_image_of):
+//   * the band plus `halo` >= W + 1 pixels either side enters LDS once, as whole 128-byte lines (the halo is a multiple of 4 pixels): 16-byte
+//     loads through a per-image raw buffer -- what lies above or below the image reads as zeros, so the pad rows need no test -- and ds_write_b128;
+//   * a wave walks the band's 32-pixel tiles (tile = wave, wave + 4, ...): the projection's weight fragment, the bias columns and the depthwise
+//     weights / bias of the lane's channel half (selected ONCE, kept in registers) are set up once per band and not once per 32 pixels;
+//   * the nine taps are ds_read_b128 at per-lane offsets that do not change from tile to tile (one 32-bit add per tap); columns -1 and W are
+//     masked by ADDRESS -- the lane reads a zero slot instead -- so no select touches freshly loaded data;
+//   * the residual is the staged centre pixel read in the accumulator's layout (ds_read_b64): the global residual loads are gone.
+// Swizzle: ds_read_b128 serves a wave in four groups of 16 lanes ({0-3, 12-15, 20-27} + ...) over 64 banks = 16 chunks of 16 bytes. A wave's tap
+// is 1 KB of consecutive chunks (2 KSF per pixel), lane (r, hh) on chunk 2 KSF (s + r) + 2 ks + hh: within a group the chunks collide in pairs
+// (KSF = 1) or fours (KSF = 2) whatever the tap's shift s. Chunk c is therefore kept at c ^ ((c >> 4) & (2 KSF - 1)): the pixels of a group that
+// share (pixel mod 8 / KSF) differ in exactly the bits that are folded in, every tap of every tile is conflict-free, and because a wave's next
+// tile is 128 pixels further the folded bits are per-lane constants (they live in the tap offsets).
+// Arithmetic: bias first, taps in (ky, kx) order through v_fma_mix_f32, dn_act_n, one rounding, the projection with its bias step, act16, the
+// residual in fp32, the permlane epilogue -- the body above, value for value; tests/test_gpu_pw_dw_lds.py holds both to the two-launch pair bit for bit.
+// Measured (profiles/pw_dw_lds_ab.txt; 64 images, 160 x 160 x 16): 35.3 -> 25.9 us per launch with one forward at a time, 47.3 -> 40.1 with three
+// in flight (rocprofv3); vector-memory read instructions 768 000 -> 102 400 per launch (15 per 32-pixel tile -> 10 per wave and band), L1 accesses
+// 17.4 M -> 2.25 M; LDS: 3.0 M cycles of which 0.33 M bank conflicts (the 8-byte residual reads, two-way; the taps have none). 122 registers, no
+// scratch, four workgroups per compute unit. What the loop leaves per tile is about 160 vector instructions, 72 of them the depthwise multiply-adds:
+// the launch is closer to vector-issue than to its memory bound now. Band length: 640 pixels on the 160-wide map (31 KB: halo 1.5 x) beat 320, 512,
+// 800 and 1280 alone on the chip (30.6 against 35.5 / 32.1 / 34.0 / 35.1 us); keeping the depthwise weights in scalar registers and selecting
+// per tile (91 registers, five workgroups per compute unit) was slower (36.3 us): residency is not what this launch lacks.
+constexpr int PW_DW_LDS_MAX = 64 * 1024;      // LDS of a workgroup: band + two halos + the zero slot (launch_pw_dw_direct falls back to the body above beyond it)
+
+__device__ __forceinline__ void fma_mix_h8_from(float (&acc)[8], const float (&c)[8], const uint4& e, const uint4& w) {
+    // acc = c + e * w: fma_mix_h8's first step without the copy of c
+    const unsigned ee[4] = {e.x, e.y, e.z, e.w}, ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        asm volatile("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,1,0]" : "=v"(acc[2 * i]) : "v"(ee[i]), "v"(ww[i]), "v"(c[2 * i]));
+        asm volatile("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,1,0]" : "=v"(acc[2 * i + 1]) : "v"(ee[i]), "v"(ww[i]), "v"(c[2 * i + 1]));
+    }
+}
+
+template <int KSF>
+__global__ __launch_bounds__(256, KSF == 1 ? 4 : 2) void pw_dw_direct_lds_kernel(PwDwArgs q, int n, int bands, int band, int halo) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pdl_lds[];
+    constexpr int PB = 32 * KSF;                           // bytes per pixel
+    constexpr unsigned SWM = 2 * KSF - 1;                  // chunk bits of a pixel: byte address A lives at A ^ (((A >> 8) & SWM) << 4)
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const PwArgs& a = q.pw;
+    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int K = 16 * KSF;
+    const int NC = a.cout;
+    int img, bi;
+    if (!xcd_image_of(blockIdx.x, bands, a.xq, n, img, bi)) return;      // workgroup-uniform
+    const int b0 = bi * band, blen = min(band, a.hw - b0);               // the band: pixels [b0, b0 + blen) of the image
+    const int nslots = blen + 2 * halo;                                  // slot s holds pixel b0 - halo + s
+    const unsigned zoff = (unsigned)nslots * PB;                         // the zero slot: 64 bytes, so that a K step's chunk bit stays inside it
+    // ---- staging: every 16-byte chunk of the slots, eight requests per thread in flight (a 640-pixel band of the 160-wide map: one batch)
+    {
+        const __amdgpu_buffer_rsrc_t xrs =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.x + (size_t)img * a.hw * K), 0, a.hw * PB, 0x00020000);
+        const int chunks = nslots * (2 * KSF);
+        const unsigned g0 = (unsigned)((b0 - halo) * PB);                // byte offset of slot 0 in the image: "negative" = far out of range = zeros
+        for (int c0 = threadIdx.x; c0 < chunks; c0 += 8 * 256) {
+            u32x4 v[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int c = c0 + i * 256;
+                v[i] = __builtin_amdgcn_raw_buffer_load_b128(xrs, c < chunks ? g0 + (unsigned)c * 16u : 0x80000000u, 0, 0);
+            }
+            // (pinned: left alone, every request sinks into the guarded store that uses it, one round trip after the other)
+            asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const unsigned A = (unsigned)(c0 + i * 256) * 16u;
+                if (c0 + i * 256 < chunks) *reinterpret_cast<u32x4*>(pdl_lds + (A ^ (((A >> 8) & SWM) << 4))) = v[i];
+            }
+        }
+        if (threadIdx.x < 4) *reinterpret_cast<u32x4*>(pdl_lds + zoff + threadIdx.x * 16) = u32x4{0u, 0u, 0u, 0u};
+    }
+    // ---- once per band: the projection's operands, the depthwise weights / bias of this lane's channel half
+    const int nrow = min(r, NC - 1);
+    const half_t* wpt = a.w + (size_t)nrow * K + hh * 8;
+    half8 wf[KSF];
+#pragma unroll
+    for (int ks = 0; ks < KSF; ++ks) wf[ks] = *reinterpret_cast<const half8*>(wpt + ks * 16);
+    const float bl = a.bias[nrow];
+    typedef unsigned u4v __attribute__((ext_vector_type(4)));
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(4))) u4v* cp4;
+    typedef const __attribute__((address_space(4))) f4v* cpf4;
+    uint4 wsel[KSF][9];
+    float bsel[KSF][8];
+#pragma unroll
+    for (int ks = 0; ks < KSF; ++ks) {
+        const cpf4 bp = (cpf4)(q.bd + ks * 16);
+        const f4v c0 = bp[0], c1 = bp[1], c2 = bp[2], c3 = bp[3];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { bsel[ks][e] = hh ? c2[e] : c0[e]; bsel[ks][4 + e] = hh ? c3[e] : c1[e]; }
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const cp4 wp = (cp4)(q.wd + t * K + ks * 16);
+            const u4v w0 = wp[0], w1 = wp[1];
+            wsel[ks][t] = make_uint4(hh ? w1[0] : w0[0], hh ? w1[1] : w0[1], hh ? w1[2] : w0[2], hh ? w1[3] : w0[3]);
+        }
+    }
+    const half8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    const half8 ones = {(half_t)1.f, (half_t)1.f, 0, 0, 0, 0, 0, 0};
+    const half_t bhi = (half_t)bl;
+    const half8 bw = {bhi, (half_t)(bl - (float)bhi), 0, 0, 0, 0, 0, 0};
+    const bool bcol = hh == 0;                             // (kb == K: hh = 0 carries the bias columns, hh = 1 zeros)
+    const half8 wlast = bcol ? bw : zero8, xlast = bcol ? ones : zero8;
+    const bool has_res = a.residual != nullptr;
+    // per-lane tap offsets relative to the lane's own slot: the tap's pixel shift plus this lane's chunk with the swizzle bits of the tap's slot
+    // folded in. Those bits are bits 3 (KSF = 1) / 2..3 (KSF = 2) of the slot index, and a wave's tiles are 128 slots apart: constants.
+    int toff[9], roff;
+    {
+        const int s0 = wave * 32 + r + halo;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int d = (t / 3 - 1) * q.w + (t % 3 - 1);
+            const unsigned sw = (((unsigned)(s0 + d) * PB >> 8) & SWM) << 4;
+            toff[t] = d * PB + (int)((unsigned)(hh * 16) ^ sw);
+        }
+        roff = (int)((((unsigned)s0 * PB >> 8) & SWM) << 4);            // the centre slot's bits, for the residual's chunks
+    }
+    __syncthreads();
+    half_t* const obase = reinterpret_cast<half_t*>(a.out) + ((size_t)img * a.hw + b0) * NC + hh * 8;
+    const int ntiles = (blen + 31) >> 5;
+    for (int t = wave; t < ntiles; t += 4) {
+        const int pl = t * 32 + r, plc = min(pl, blen - 1);               // this lane's pixel in the band (a ragged last tile: clamped, not stored)
+        const unsigned p = (unsigned)(b0 + plc);
+        const int px = (int)(p - fd_div(p, q.fd_w) * (unsigned)q.w);
+        const bool okl = px > 0, okr = px < q.w - 1;
+        const unsigned S = (unsigned)(plc + halo) * PB;
+        // (a clamped lane keeps the offsets of its unclamped slot: its folded bits may differ from its slot's, which only permutes the chunks of pixels
+        // that ARE staged -- the lane's values are never stored)
+        unsigned ad[9];
+#pragma unroll
+        for (int tp = 0; tp < 9; ++tp) {
+            const unsigned A = S + (unsigned)toff[tp];
+            ad[tp] = (tp % 3 == 0) ? (okl ? A : zoff) : (tp % 3 == 2) ? (okr ? A : zoff) : A;
+        }
+        half8 xf[KSF];
+#pragma unroll
+        for (int ks = 0; ks < KSF; ++ks) {
+            half8 xin[9];
+            // (chunk 2 ks + hh with the slot's bits folded in: everything else in the address is a multiple of 64, so the K step is bit 5)
+#pragma unroll
+            for (int tp = 0; tp < 9; ++tp) xin[tp] = *reinterpret_cast<const half8*>(pdl_lds + (ad[tp] ^ (unsigned)(ks * 32)));
+            float acc[8];
+            fma_mix_h8_from(acc, bsel[ks], *reinterpret_cast<const uint4*>(&xin[0]), wsel[ks][0]);
+#pragma unroll
+            for (int tp = 1; tp < 9; ++tp) fma_mix_h8(acc, *reinterpret_cast<const uint4*>(&xin[tp]), wsel[ks][tp]);
+            dn_act_n<float[8], 8>(acc, q.act_dw);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xf[ks][e] = (half_t)acc[e];
+        }
+        uint2 rres[2 * KSF];
+        if (has_res) {
+            // channels 8 g + 4 hh .. + 3 of the centre pixel = chunk g, bytes 8 hh .. (a residual means cout == cin: groups beyond 2 KSF do not exist)
+#pragma unroll
+            for (int g = 0; g < 2 * KSF; ++g) rres[g] = *reinterpret_cast<const uint2*>(pdl_lds + S + ((unsigned)(g * 16) ^ (unsigned)roff) + hh * 8);
+        }
+        floatx16 acc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KSF; ++ks) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[ks], xf[ks], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlast, xlast, acc, 0, 0, 0);
+        act16(acc, a.act);
+        if (has_res) {
+#pragma unroll
+            for (int g = 0; g < 2 * KSF; ++g) {
+                const half4 rr = __builtin_bit_cast(half4, rres[g]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[4 * g + e] += (float)rr[e];
+            }
+        }
+        uint2v pk[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            half4 hv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) hv[e] = (half_t)acc[4 * g + e];
+            pk[g] = __builtin_bit_cast(uint2v, hv);
+        }
+        const uint2v s0 = __builtin_amdgcn_permlane32_swap(pk[0][0], pk[1][0], false, false);
+        const uint2v s1 = __builtin_amdgcn_permlane32_swap(pk[0][1], pk[1][1], false, false);
+        const uint2v s2 = __builtin_amdgcn_permlane32_swap(pk[2][0], pk[3][0], false, false);
+        const uint2v s3 = __builtin_amdgcn_permlane32_swap(pk[2][1], pk[3][1], false, false);
+        const uint4 lo4 = make_uint4(s0[0], s1[0], s0[1], s1[1]), hi4 = make_uint4(s2[0], s3[0], s2[1], s3[1]);
+        half_t* orow = obase + (size_t)pl * NC;
+        const int c0 = hh * 8;
+        if (pl < blen) {
+            if (c0 < NC) *reinterpret_cast<uint4*>(orow) = lo4;
+            if (c0 + 16 < NC) *reinterpret_cast<uint4*>(orow + 16) = hi4;
+        }
+    }
+}
+
 
 // Weight-stationary variant for the EXPANSIONS (round 6): cin <= 128, no squeeze-excitation scale, no residual -- 24 -> 72 on the 80 x 80 map,
 // 40 -> 120, 80 -> 480, 112 -> 672 (mobilenetv3.py:76 expand ConvBNActivation) and the V2 expansions that run as launches of their own.
@@ -677,6 +875,19 @@ bool pw_dw_direct_supported(const PwArgs& a, const DwArgs& d) {
            a.hw >= 32 && fd_ok((unsigned long long)a.hw, (unsigned)d.w_);
 }
 
+// The LDS body's geometry (pw_dw_direct_lds_kernel): band length, halo and LDS bytes of a workgroup; false where the staging does not fit
+// (a band plus two halos of W + 1 pixels beyond PW_DW_LDS_MAX: very wide maps) or the per-image raw buffer's 32-bit byte offsets would not hold.
+struct PwDwLds { int band, halo, bands, lds; };
+static bool pw_dw_lds_geometry(const PwArgs& a, const DwArgs& d, PwDwLds& g) {
+    const int pb = a.cin * 2;
+    g.band = std::max(32, dn_knob("DN_PW_DW_BAND", DN_PW_DW_BAND) & ~31);      // (whole 32-pixel tiles: only an image's last band is ragged)
+    g.halo = (d.w_ + 1 + 3) & ~3;
+    g.bands = dn_cdiv(a.hw, g.band);
+    const long lds = ((long)std::min(g.band, a.hw) + 2L * g.halo) * pb + 64;
+    g.lds = (int)std::min(lds, (long)PW_DW_LDS_MAX + 1);
+    return lds <= PW_DW_LDS_MAX && (long)a.hw * pb < (1L << 31) && (long)(d.n + 7) * g.bands < (1L << 31);
+}
+
 int launch_pw_dw_direct(const PwArgs& a, const DwArgs& d, hipStream_t s) {
     DN_REQUIRE(pw_dw_direct_supported(a, d), "depthwise + pointwise (direct): unsupported cin=%d cout=%d", a.cin, a.cout);
     PwDwArgs q{};
@@ -684,9 +895,16 @@ int launch_pw_dw_direct(const PwArgs& a, const DwArgs& d, hipStream_t s) {
     q.pw.x = d.x;
     q.wd = d.w; q.bd = d.bias; q.h = d.h; q.w = d.w_; q.act_dw = d.act;
     q.inv_hw = 1.0f / (float)a.hw; q.fd_w = fastdiv((unsigned)d.w_);
+    dn_note_kernel("pw_dw_direct_kernel<%d>", a.cin / 16);
+    PwDwLds g;
+    if (dn_knob("DN_PW_DW_LDS", 1) != 0 && a.m == (long)d.n * a.hw && pw_dw_lds_geometry(a, d, g)) {
+        const dim3 grid((unsigned)(a.xq > 0 ? 8 * a.xq : d.n) * g.bands);
+        if (a.cin == 16) hipLaunchKernelGGL((pw_dw_direct_lds_kernel<1>), grid, dim3(256), g.lds, s, q, d.n, g.bands, g.band, g.halo);
+        else hipLaunchKernelGGL((pw_dw_direct_lds_kernel<2>), grid, dim3(256), g.lds, s, q, d.n, g.bands, g.band, g.halo);
+        return DN_OK;
+    }
     const int tiles = a.xq > 0 ? dn_cdiv((long)a.xq * a.hw, 128) : dn_cdiv(a.m, 128);
     const dim3 grid((unsigned)(a.xq > 0 ? 8 * tiles : tiles));
-    dn_note_kernel("pw_dw_direct_kernel<%d>", a.cin / 16);
     if (a.cin == 16) hipLaunchKernelGGL((pw_dw_direct_kernel<1>), grid, dim3(256), 0, s, q, tiles);
     else hipLaunchKernelGGL((pw_dw_direct_kernel<2>), grid, dim3(256), 0, s, q, tiles);
     return DN_OK;

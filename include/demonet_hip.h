@@ -262,6 +262,17 @@ DN_API int dn_expand_depthwise(const void* x_dev, const void* w1_dev, const floa
                         void* stream);
 DN_API int dn_expand_depthwise_tiles(int ho, int wo, int stride);
 
+/* First inverted-residual block without an expansion (pwdirect.hip): depthwise 3x3 (stride 1, padding 1) wd/bd + act_dw -> 1x1 projection
+ * w/b + act (+ residual = x), BN folded; mobilenetv3.py:61-99 with expanded == input channels, mobilenetv2.py:57-84 with expand_ratio 1.
+ * The depthwise output stays in registers; the result equals dn_depthwise_conv followed by dn_pointwise_conv bit for bit.
+ * x: [n][h][w][c] fp16, wd [9][c] fp16, bd fp32 [c], w [cout][c] fp16, b fp32 [cout], out [n][h][w][cout] fp16. c in {16, 32},
+ * cout <= 32 and a multiple of 8, h * w >= 32, has_res only with cout == c; anything else returns DN_E_UNSUPPORTED.
+ * The input is staged through LDS in bands of DN_PW_DW_BAND pixels of one image (environment DN_PW_DW_LDS=0: nine global taps per pixel
+ * instead; also taken where a band and its two halos of w + 1 pixels do not fit 64 KB of LDS). */
+#define DN_PW_DW_BAND 640
+DN_API int dn_depthwise_pointwise(const void* x_dev, const void* wd_dev, const float* bd_dev, const void* w_dev, const float* b_dev,
+                           void* out_dev, int n, int h, int w, int c, int cout, int act_dw, int act, int has_res, void* stream);
+
 /* 1 = replay the launch sequence from a cached hipGraph keyed by (n, pointers) [default], 0 = eager launches */
 DN_API int dn_set_graph_mode(dn_plan* plan, int enabled);
 
