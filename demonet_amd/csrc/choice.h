@@ -11,7 +11,7 @@ struct PwChoice {
     enum Kernel {
         NONE,                                               // no kernel of the family takes the problem
         AS_POINTWISE,                                       // conv_choose: a dense 1x1 that the 1x1 family serves -- pw_choose decides, on conv_1x1_as_pw(a)
-        PW_WSTAT, PW_STREAM, PW_DIRECT,                     // pwdirect.hip: pw_wstat_kernel<KS1 = k, RT = t>, pw_stream_kernel<KSF = k, PX = t>, pw_direct_kernel<KSF = k, TC = t>
+        PW_WSTAT, PW_STREAM, PW_DIRECT,                     // pwdirect.hip: pw_wstat_kernel<KS1 = k, RT = t, false>, pw_stream_kernel<KSF = k, PX = t>, pw_direct_kernel<KSF = k, TC = t> (or, proj, its weight-stationary body)
         PW_XS, PW_TILE, PW_GROUP,                           // pointwise.hip: pw_xs_kernel<32>, pw_kernel / pw_group_kernel<bp, bc, .., conv, bk, pf, sef, fk>
         CONV_PATCH, CONV_PATCH_RESIDENT, CONV_HALO, CONV_GLDS   // convbig.hip; conv_halo_kernel<3, TP, TC, head> by halo: 1 = 256 px x 256 ch, 2 = 512 x 128, 3 = 256 x 128
     };
@@ -20,6 +20,7 @@ struct PwChoice {
     bool conv = false, sef = false, fk = false;   // implicit-GEMM body; squeeze-excitation in the prologue; the bound-test-free K loop
     int k = 0, t = 0, halo = 0;
     bool head = false, pool = false;          // fp32 head form (takes the rider w_b); writes the 2 x 2 max-pooled map (pool_out)
+    bool proj = false;                        // PW_DIRECT, t = 1: the weight-stationary body (pw_wstat_kernel<k + 1, .., PROJ>) behind the launch and its label
 };
 
 // ---- workgroup thresholds. Tile choice of the staged kernels: these GEMMs are latency/HBM-bound, not MFMA-bound, so what matters is (a) enough
@@ -69,6 +70,16 @@ inline bool pw_wstat_supported(const PwArgs& a) {
     return dn_knob("DN_PW_WSTAT", 1) != 0 && a.wfrag && !a.se && !a.residual && a.cin >= 16 && a.cin <= 128 && a.cin % 8 == 0 && a.m >= 3200 &&
            (long)a.m * a.cout * 2 < 0x7fffffffL && a.cout >= 64;
 }
+// The narrow projections (cout <= 64: one or two channel tiles, every A fragment of the layer in a wave's registers), with or without squeeze-excitation
+// scale and residual, on the same weight-stationary schedule (pw_wstat_kernel<.., PROJ = true>). A 32-row tile lies inside one image (hw % 32 == 0): one
+// scale row serves it, and its residual rows are 64 cout contiguous bytes. DN_PW_WSTAT_PROJ: 1 (default) = from PW_WSTAT_PROJ_MIN_ROWS rows, 0 = never,
+// 2 = wherever the body can run (tests, A/B).
+constexpr int PW_WSTAT_PROJ_MIN_ROWS = 51200;
+inline bool pw_wstat_proj_supported(const PwArgs& a) {
+    const int knob = dn_knob("DN_PW_WSTAT_PROJ", 1);
+    return knob != 0 && a.wfrag && a.cin >= 16 && a.cin <= 128 && a.cin % 8 == 0 && a.cout <= 64 && a.hw % 32 == 0 && (knob == 2 || a.m >= PW_WSTAT_PROJ_MIN_ROWS) &&
+           (long)a.m * a.cout * 2 < 0x7fffffffL;
+}
 // the squeeze-excitation of a projection can be computed in the projection kernel's prologue (SEF variant of the 64 x 64 tile)
 inline bool pw_sef_supported(const PwArgs& a) {
     return dn_knob("DN_SE_FOLD", 1) != 0 && !a.se && a.cin % 8 == 0 && a.sef_sq <= 32 && a.hw >= 64;
@@ -107,6 +118,10 @@ inline PwChoice pw_choose(const PwArgs& a) {
         // (measured: threshold 400 -> batch 64 1.115 -> 1.107 ms, batch 32 0.79 -> 0.77 ms; 200 and 600 in between).
         c.kernel = PwChoice::PW_DIRECT;
         c.t = (ksf <= 8 && a.cout >= PW_DIRECT_TC2_MIN_COUT) ? 2 : 1;
+        // the narrow projections with many rows (the SE-scaled 72 / 120 -> 40 of the 40 x 40 maps at batch 32 and more): the weight-stationary body behind
+        // this launch. Measured (profiles/pw_wstat_proj_ab.txt; rocprofv3, one forward at a time): 102 400 rows 120 -> 40 13.8 -> 11.2 us, 72 -> 40 9.4 -> 8.1;
+        // 51 200 rows 9.8 -> 8.4 and 5.9 -> 5.6; the step at batch 64 0.5693 -> 0.5624 ms, at batch 32 level. Fewer rows: not measured, the register-direct body stays.
+        c.proj = c.t == 1 && pw_wstat_proj_supported(a);
         return c;
     }
     if (dn_knob("DN_PW_XS", 1) && !a.sef_part && a.wfrag && a.cin % 16 == 0 && a.cin <= 1024 && a.cout <= 160 && !(a.act >> 8) &&      // (K % 16 == 8: measured slower than the tiled kernel)

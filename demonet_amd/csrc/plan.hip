@@ -1779,8 +1779,8 @@ static const char* pw_choice_name(PwChoice::Kernel k) {
     return "?";
 }
 static int pw_choice_text(const PwChoice& c, char* buf, int capacity) {
-    snprintf(buf, (size_t)capacity, "kernel=%s tile=%dx%d bk=%d pf=%d conv=%d sef=%d fk=%d k=%d t=%d halo=%d head=%d pool=%d", pw_choice_name(c.kernel), c.bp, c.bc,
-             c.bk, c.pf, (int)c.conv, (int)c.sef, (int)c.fk, c.k, c.t, c.halo, (int)c.head, (int)c.pool);
+    snprintf(buf, (size_t)capacity, "kernel=%s tile=%dx%d bk=%d pf=%d conv=%d sef=%d fk=%d k=%d t=%d halo=%d head=%d pool=%d proj=%d", pw_choice_name(c.kernel), c.bp, c.bc,
+             c.bk, c.pf, (int)c.conv, (int)c.sef, (int)c.fk, c.k, c.t, c.halo, (int)c.head, (int)c.pool, (int)c.proj);
     return DN_OK;
 }
 

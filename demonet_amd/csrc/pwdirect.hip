@@ -727,7 +727,13 @@ __device__ __forceinline__ void pw_glds16(const void* gsrc, unsigned dst) {
                  : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
 }
 
-template <int KS1, int RT>
+//
+// PROJ (the narrow projections, cout <= 64: runs == 1, RT = every channel tile of the layer; pw_wstat_proj_supported): the same walk with pw_direct_kernel<KSF, 1>'s
+// squeeze-excitation scale and residual. hw % 32 == 0, so a tile lies inside one image: the K floats of that image's scale row and the tile's residual rows
+// (32 x cout x 2 contiguous bytes) are requested WITH the tile's x into the wave's buffer ([x: ksw KB][scale: 1 KB][residual: 64 cout bytes in 1 KB pieces]) and
+// read back with it -- the scale row in front of the B fragments ((half)((float)x * s): v_mul_f32 + v_cvt_f16_f32, the rounding of pw_direct_kernel), the residual in
+// the accumulator layout, added in fp32 behind the activation. Same K order, same rounding points: bit-identical to pw_direct_kernel (tests/test_gpu_pw_wstat_proj.py).
+template <int KS1, int RT, bool PROJ>
 __global__ __launch_bounds__(256) void pw_wstat_kernel(PwArgs a, int runs, int wg_per_group) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pws_lds[];
     constexpr int KSF = KS1 - 1;
@@ -752,13 +758,29 @@ __global__ __launch_bounds__(256) void pw_wstat_kernel(PwArgs a, int runs, int w
     const int ctiles = (NC + 31) >> 5;
     const int ct0 = run * RT;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)pws_lds;
-    const unsigned xoff = (unsigned)(RT * ksw * 1024 + wave * ksw * 1024);          // this wave's x buffer: ksw pieces of 1 KB >= 64 K bytes
+    const int rkb = PROJ ? (NC * 64 + 1023) >> 10 : 0;                                // PROJ: 1 KB pieces of a tile's residual rows
+    const int wbuf = (ksw + (PROJ ? 1 + rkb : 0)) * 1024;
+    const unsigned xoff = (unsigned)(RT * ksw * 1024 + wave * wbuf);                // this wave's x buffer: ksw pieces of 1 KB >= 64 K bytes
+    const unsigned soff = xoff + (unsigned)ksw * 1024u, roff = soff + 1024u;        // PROJ: the scale row and the residual rows behind it
+    const bool has_se = PROJ && a.se != nullptr, has_res = PROJ && a.residual != nullptr;
     auto dma_x = [&](int u) {
         const long row0 = (long)r0 + (long)u * 32;
         const unsigned char* src = reinterpret_cast<const unsigned char*>(a.x + row0 * K);
         const unsigned lim = (unsigned)min((long)(a.m - row0) * K * 2 - 16, 0x7fffffffL);           // the last 16 bytes of the tensor
 #pragma unroll 1
         for (int p = 0; p < ksw; ++p) pw_glds16(src + min((unsigned)(p * 1024 + lane * 16), lim), lds0 + xoff + p * 1024);
+        if constexpr (PROJ) {
+            if (has_se) {        // (the lanes beyond the row's 4 K bytes fetch its last 16 again)
+                const unsigned char* ssrc = reinterpret_cast<const unsigned char*>(a.se + (size_t)((int)row0 / a.hw) * K);
+                pw_glds16(ssrc + min((unsigned)(lane * 16), (unsigned)(K * 4 - 16)), lds0 + soff);
+            }
+            if (has_res) {
+                const unsigned char* rsrc = reinterpret_cast<const unsigned char*>(a.residual + row0 * NC);
+                const unsigned rlim = (unsigned)min((long)(a.m - row0) * NC * 2 - 16, 0x7fffffffL);
+#pragma unroll 1
+                for (int p = 0; p < rkb; ++p) pw_glds16(rsrc + min((unsigned)(p * 1024 + lane * 16), rlim), lds0 + roff + p * 1024);
+            }
+        }
     };
     int u = wgq * 4 + wave;
     if (u < n_units) dma_x(u);
@@ -799,8 +821,36 @@ __global__ __launch_bounds__(256) void pw_wstat_kernel(PwArgs a, int runs, int w
         half8 xf[KS1];
 #pragma unroll
         for (int ks = 0; ks < KS1; ++ks) xf[ks] = *reinterpret_cast<const half8*>(pws_lds + xrd + (ks < KSF ? (unsigned)(ks * 32 + hh * 16) : xlast));
+        float4 sv[PROJ ? KS1 : 1][2];
+        uint2 rres[RT][4];
+        if constexpr (PROJ) {
+            if (has_se) {
+#pragma unroll
+                for (int ks = 0; ks < KS1; ++ks) {        // this lane's columns of the step: what pw_direct_kernel reads from a.se
+                    const float4* sp = reinterpret_cast<const float4*>(pws_lds + soff + (ks < KSF ? (unsigned)(ks * 64 + hh * 32) : 2u * xlast));
+                    sv[ks][0] = sp[0]; sv[ks][1] = sp[1];
+                }
+            }
+            if (has_res) {
+                const unsigned char* rp = pws_lds + roff + (unsigned)r * (unsigned)NC * 2u;
+#pragma unroll
+                for (int t = 0; t < RT; ++t)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) rres[t][g] = *reinterpret_cast<const uint2*>(rp + min((ct0 + t) * 32 + 8 * g + 4 * hh, NC - 4) * 2);
+            }
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (u + Q < n_units) dma_x(u + Q);
+        if constexpr (PROJ) {
+            if (has_se) {
+#pragma unroll
+                for (int ks = 0; ks < KS1; ++ks) {
+                    const float s[8] = {sv[ks][0].x, sv[ks][0].y, sv[ks][0].z, sv[ks][0].w, sv[ks][1].x, sv[ks][1].y, sv[ks][1].z, sv[ks][1].w};
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) xf[ks][e] = (half_t)((float)xf[ks][e] * s[e]);
+                }
+            }
+        }
         xf[KSF] = data ? xf[KSF] : (bcol ? ones : zero8);
         const int rr = r0 + u * 32 + (lane & 15);
 #pragma unroll
@@ -811,6 +861,16 @@ __global__ __launch_bounds__(256) void pw_wstat_kernel(PwArgs a, int runs, int w
 #pragma unroll
             for (int ks = 0; ks < KS1; ++ks) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[t][ks], xf[ks], acc, 0, 0, 0);
             act16(acc, act);
+            if constexpr (PROJ) {
+                if (has_res) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const half4 rq = __builtin_bit_cast(half4, rres[t][g]);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) acc[4 * g + e] += (float)rq[e];
+                    }
+                }
+            }
             uint2v p[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -842,6 +902,25 @@ __global__ __launch_bounds__(256) void pw_wstat_kernel(PwArgs a, int runs, int w
 }
 
 template <int KS1, int RT>
+int launch_wstat_proj_t(const PwArgs& a, hipStream_t s) {
+    const int groups = a.xq > 0 ? 8 : 1;
+    const long rows = a.xq > 0 ? (long)a.xq * a.hw : a.m;
+    const int units = dn_cdiv(rows, 32);
+    const int ksw = dn_cdiv(a.cin, 16);
+    const int lds = (RT * ksw + 4 * (ksw + 1 + dn_cdiv(a.cout * 64, 1024))) * 1024;
+    // workgroups per group of rows: two per compute unit (64 KB of LDS at 120 -> 40), fewer when there are not that many pixel tiles. Measured at 400 tiles per
+    // group (profiles/pw_wstat_proj_ab.txt, 120 -> 40 / 72 -> 40, us): 64 per group 11.15 / 7.92, 50 (every wave two tiles) 10.98 / 8.18, 32 12.10 / 9.29, 96 12.27 / 9.14.
+    // DN_PW_WSTAT_PROJ_WGS (workgroups per launch) is there for that sweep and for the tests, which shrink the grid so that a wave walks many tiles.
+    const int wpg = std::max(1, std::min(std::max(1, dn_knob("DN_PW_WSTAT_PROJ_WGS", 512)) / groups, dn_cdiv(units, 4)));
+    if (lds > 64 * 1024) DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(pw_wstat_kernel<KS1, RT, true>)));
+    // The label stays that of the launch whose body this replaces (pw_direct_kernel<KSF, 1>): the plan's launch list, its owners and bench.py's families
+    // know the launch by it (tests/test_gpu_plan_signature.py).
+    dn_note_kernel("pw_direct_kernel<%d,%d>", KS1 - 1, 1);
+    hipLaunchKernelGGL((pw_wstat_kernel<KS1, RT, true>), dim3((unsigned)(groups * wpg)), dim3(256), lds, s, a, 1, wpg);
+    return DN_OK;
+}
+
+template <int KS1, int RT>
 int launch_wstat_t(const PwArgs& a, hipStream_t s) {
     const int ctiles = dn_cdiv(a.cout, 32), runs = dn_cdiv(ctiles, RT);
     const int groups = a.xq > 0 ? 8 : 1;
@@ -853,7 +932,7 @@ int launch_wstat_t(const PwArgs& a, hipStream_t s) {
     const int ksw = dn_cdiv(a.cin, 16);
     const int lds = (RT + 4) * ksw * 1024;
     dn_note_kernel("pw_wstat_kernel<%d,%d>", KS1, RT);
-    hipLaunchKernelGGL((pw_wstat_kernel<KS1, RT>), dim3((unsigned)(groups * wpg)), dim3(256), lds, s, a, runs, wpg);
+    hipLaunchKernelGGL((pw_wstat_kernel<KS1, RT, false>), dim3((unsigned)(groups * wpg)), dim3(256), lds, s, a, runs, wpg);
     return DN_OK;
 }
 
@@ -940,6 +1019,13 @@ int launch_pw_direct(const PwArgs& a, const PwChoice& c, hipStream_t s) {
 #define DN_PWD_CASE2(k) case k: return launch_t<k, 2>(a, wc_log, s);
             DN_PWD_CASE2(0) DN_PWD_CASE2(1) DN_PWD_CASE2(2) DN_PWD_CASE2(3) DN_PWD_CASE2(4) DN_PWD_CASE2(5) DN_PWD_CASE2(6) DN_PWD_CASE2(7) DN_PWD_CASE2(8)
 #undef DN_PWD_CASE2
+        }
+    } else if (c.kernel == PwChoice::PW_DIRECT && c.proj) {
+        // the weight-stationary body of the narrow projections: KS1 = k + 1 steps, every channel tile of the layer (one or two) in the wave
+        switch ((c.k + 1) * 10 + ctiles) {
+#define DN_PWP_CASE(k) case k * 10 + 1: return launch_wstat_proj_t<k, 1>(a, s); case k * 10 + 2: return launch_wstat_proj_t<k, 2>(a, s);
+            DN_PWP_CASE(2) DN_PWP_CASE(3) DN_PWP_CASE(4) DN_PWP_CASE(5) DN_PWP_CASE(6) DN_PWP_CASE(7) DN_PWP_CASE(8) DN_PWP_CASE(9)
+#undef DN_PWP_CASE
         }
     } else if (c.kernel == PwChoice::PW_DIRECT) {
         const int wc_log = ctiles <= 1 ? 0 : ctiles <= 2 ? 1 : 2;
