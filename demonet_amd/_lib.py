@@ -16,6 +16,7 @@ DN_COLOR_FULL_RANGE = 0x10
 DN_REGION_HFLIP = 1
 DN_SGD_CHUNK = 2048
 DN_SGD_MAX_GATE = 8
+DN_ZONE = dict(cross=1, enter=2, exit=3, vanish=4)
 
 
 class TensorDesc(C.Structure):
@@ -54,6 +55,11 @@ class TrackParams(C.Structure):
     _fields_ = [("track_thresh", C.c_float), ("low_thresh", C.c_float), ("new_thresh", C.c_float),
                 ("match_thresh", C.c_float), ("second_thresh", C.c_float), ("unconfirmed_thresh", C.c_float),
                 ("track_buffer", C.c_int32), ("class_agnostic", C.c_int32), ("max_tracks", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ZoneConfig(C.Structure):
+    _fields_ = [("n_lines", C.c_int32), ("lines", C.c_float * 4 * 16), ("n_zones", C.c_int32), ("nv", C.c_int32 * 16),
+                ("verts", C.c_float * 2 * 16 * 16), ("reserved", C.c_int32 * 2)]
 
 
 class ModelDesc(C.Structure):
@@ -137,6 +143,10 @@ _SIGNATURES = {
     "dn_track_state_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "dn_track_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dn_track_update": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(TrackParams), C.c_void_p, C.c_size_t] + [C.c_void_p] * 8),
+    "dn_zone_state_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "dn_zone_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dn_zone_update": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 # include/demonet_hip_debug.h: test support beside the boundary (not part of EXPORTS, which mirrors demonet_hip.h)

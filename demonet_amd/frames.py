@@ -196,15 +196,18 @@ def forward_frames(model, batch: FrameBatch, packed=None):
     return b["outs"]
 
 
-def track_frames(model, batch: FrameBatch, tracker):
+def track_frames(model, batch: FrameBatch, tracker, analytics=None):
     """SSD.track_frames (see there)."""
-    from .track import ByteTracker
+    from .track import ByteTracker, with_analytics
     if model.training:
         raise ValueError("track_frames: the model must be in eval mode")
     if not isinstance(tracker, ByteTracker):
         raise ValueError("track_frames: tracker must be a ByteTracker, got {}".format(type(tracker)))
+    if analytics is not None:
+        from .zones import check_analytics
+        check_analytics(analytics, tracker, "track_frames")
     boxes, scores, labels, counts = forward_frames(model, batch)
-    return tracker.update(boxes, scores, labels, counts)
+    return with_analytics(tracker.update(boxes, scores, labels, counts), analytics)
 
 
 # ---------------------------------------------------------------------------------------------------------------- regions (DESIGN 4q)

@@ -323,13 +323,16 @@ def detect_sliced_frames(model, batch, tile=None, overlap: float = 0.25, full_im
     return [{"boxes": boxes[g, :c], "scores": scores[g, :c], "labels": labels[g, :c]} for g, c in enumerate(cnt)]
 
 
-def track_sliced_frames(model, batch, tracker, slicer: FrameSlicer):
+def track_sliced_frames(model, batch, tracker, slicer: FrameSlicer, analytics=None):
     """SSD.track_sliced_frames (see there)."""
-    from .track import ByteTracker, MAX_D as TRACK_MAX_D
+    from .track import ByteTracker, MAX_D as TRACK_MAX_D, with_analytics
     if not isinstance(tracker, ByteTracker):
         raise ValueError("track_sliced_frames: tracker must be a ByteTracker, got {}".format(type(tracker)))
     if not isinstance(slicer, FrameSlicer) or slicer.model is not model:
         raise ValueError("track_sliced_frames: slicer must be a FrameSlicer of this model")
     if slicer.D > TRACK_MAX_D:
         raise ValueError("track_sliced_frames: detections_per_img = {} rows per frame, the tracker takes at most {}".format(slicer.D, TRACK_MAX_D))
-    return tracker.update(*slicer(batch))
+    if analytics is not None:
+        from .zones import check_analytics
+        check_analytics(analytics, tracker, "track_sliced_frames")
+    return with_analytics(tracker.update(*slicer(batch)), analytics)

@@ -392,13 +392,16 @@ class SSD(_Tracked):
         from .fusion import detect_tta
         return detect_tta(self, images, hflip, fuse, thresh, skip_thresh)
 
-    def track(self, images: Tensor, tracker):
+    def track(self, images: Tensor, tracker, analytics=None):
         """Detect and track one frame of every stream (demonet_amd/track.py): forward_batch on images [B, 3, H, W], image b being the
         current frame of stream b, then tracker.update (a ByteTracker with B streams on the same device) on the detections where they lie: one
         more launch behind the forward, no device-to-host copy. Returns what ByteTracker.update returns: padded device tensors (boxes [B, T, 4],
-        scores, labels, ids, det [B, T], counts [B], det_ids [B, D]) of the confirmed tracks seen in this frame. Eval mode only."""
+        scores, labels, ids, det [B, T], counts [B], det_ids [B, D]) of the confirmed tracks seen in this frame. Eval mode only.
+        analytics: None, or a zones.ZoneAnalytics bound to this tracker: its step -- line crossings, zone entries, exits and dwell,
+        accumulated on the device -- follows the tracker's on the same stream, and the return value gains the pair (events [B, max_events, 8],
+        event_counts [B]) as its last element. With None the call, its launches and its results are exactly those without the argument."""
         from .track import track
-        return track(self, images, tracker)
+        return track(self, images, tracker, analytics)
 
     def forward_frames(self, batch, packed: Optional[Tensor] = None):
         """The forward on video surfaces (demonet_amd/frames.py): batch is a FrameBatch naming n NV12 / I420 / RGB24 / BGR24 frames, each
@@ -410,10 +413,11 @@ class SSD(_Tracked):
         from .frames import forward_frames
         return forward_frames(self, batch, packed)
 
-    def track_frames(self, batch, tracker):
-        """`track` on top of forward_frames: frame b of the FrameBatch is the current frame of stream b. Returns what ByteTracker.update returns."""
+    def track_frames(self, batch, tracker, analytics=None):
+        """`track` on top of forward_frames: frame b of the FrameBatch is the current frame of stream b. Returns what ByteTracker.update returns;
+        analytics as in `track`."""
         from .frames import track_frames
-        return track_frames(self, batch, tracker)
+        return track_frames(self, batch, tracker, analytics)
 
     def forward_regions(self, batch, table, packed: Optional[Tensor] = None):
         """The forward on REGIONS of video surfaces (demonet_amd/frames.py): table is a frames.RegionTable of n (frame, x0, y0, w, h[,
@@ -440,12 +444,12 @@ class SSD(_Tracked):
         from .fusion import detect_tta_frames
         return detect_tta_frames(self, batch, fuse, thresh, skip_thresh)
 
-    def track_sliced_frames(self, batch, tracker, slicer):
+    def track_sliced_frames(self, batch, tracker, slicer, analytics=None):
         """Video -> tiles -> merge -> ByteTrack without a host wait per frame step: tracker.update(*slicer(batch)) for a sliced.FrameSlicer of
-        this model (frame g of the batch is the current frame of stream g). Returns what ByteTracker.update returns. ValueError when
-        detections_per_img exceeds the tracker's 512 rows."""
+        this model (frame g of the batch is the current frame of stream g). Returns what ByteTracker.update returns; analytics as in `track`.
+        ValueError when detections_per_img exceeds the tracker's 512 rows."""
         from .sliced import track_sliced_frames
-        return track_sliced_frames(self, batch, tracker, slicer)
+        return track_sliced_frames(self, batch, tracker, slicer, analytics)
 
     def batch_split(self, n: int) -> int:
         """Number of parallel sub-batch launch chains a forward of n images is issued as (1 = a single chain)."""

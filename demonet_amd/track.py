@@ -160,11 +160,22 @@ class ByteTracker:
         self.state.copy_(st)
 
 
-def track(model, images: Tensor, tracker: ByteTracker):
+def with_analytics(outs, analytics):
+    """The tracker step's outputs, or -- with a zones.ZoneAnalytics -- those followed by the analytics step's (events, event_counts): the step is
+    enqueued behind the tracker's on the same (the current) stream."""
+    if analytics is None:
+        return outs
+    return tuple(outs) + (analytics.update(),)
+
+
+def track(model, images: Tensor, tracker: ByteTracker, analytics=None):
     """SSD.track (see there)."""
     if model.training:
         raise ValueError("track: the model must be in eval mode")
     if not isinstance(tracker, ByteTracker):
         raise ValueError("track: tracker must be a ByteTracker, got {}".format(type(tracker)))
+    if analytics is not None:
+        from .zones import check_analytics
+        check_analytics(analytics, tracker, "track")
     boxes, scores, labels, counts = model.forward_batch(images)
-    return tracker.update(boxes, scores, labels, counts)
+    return with_analytics(tracker.update(boxes, scores, labels, counts), analytics)

@@ -643,6 +643,65 @@ DN_API int dn_track_update(const float* boxes_dev, const float* scores_dev, cons
                            int64_t* labels_out_dev, int64_t* ids_out_dev, int32_t* det_out_dev, int32_t* counts_out_dev, int64_t* det_ids_out_dev,
                            void* stream);
 
+/* Line-crossing and zone analytics behind the tracker (csrc/zones.hip): per stream up to 16 directed lines and 16 polygon zones;
+ * counters and a short event list accumulate on the device, ONE more small launch per frame step. demonet_amd/zones.py (ZoneAnalytics) is the
+ * caller. dn_zone_update runs after dn_track_update on the same stream and READS the tracker's state as documented above (the header words and the
+ * per-slot arrays state, id, label, filter, last_frame of Tp entries); it never writes it. The configuration and the class map lie in device
+ * memory, so a captured step follows edits made between replays.
+ * config_dev: [streams] dn_zone_config, coordinates in frame pixels (the coordinates of the tracker's boxes). n_lines, n_zones and nv come from
+ * device memory, so the kernel clamps them: n_lines and n_zones to 0 .. 16, every nv to 3 .. 16 (the caller validates them before upload).
+ * class_bin_dev: [n_labels] uint8. A track of label l counts in bin class_bin[l], 0 .. 7; the value 255 (and any value above 7), or l outside
+ * [0, n_labels), means the track is ignored. NULL: every label goes to bin 0.
+ * anchor: 0 the box centre ((x1 + x2) * 0.5f, (y1 + y2) * 0.5f), 1 the bottom centre ((x1 + x2) * 0.5f, y2); (x1, y1, x2, y2) is the tracker's
+ * mean -> box of the slot's filter, in its operation order. All arithmetic is fp32 with one rounding per operation, the divide correctly rounded.
+ * A step, per stream. f is the tracker's frame word, T the tracker's fields of slot s, Z the zone state's:
+ *   1. per slot s < max_tracks: if T.state == 0 or T.id != Z.id[s], the old entry is closed: for every zone bit z set in Z.inside,
+ *      vanished[z][Z.bin] goes up by one and a VANISH event is emitted with dwell f - enter_frame[z] (label -1: the state keeps no label; Z.bin is
+ *      taken modulo 8). The entry then becomes (id = T.state ? T.id : 0, has_prev = 0, inside = 0); its other fields stay;
+ *   2. the slot is OBSERVED iff T.state == 2, T.last_frame == f, its bin is not 255, and both anchor coordinates are finite. A slot that is not
+ *      observed does nothing further and counts in no occupancy. When the slot is observed, Z.bin is set;
+ *   3. lines apply only with has_prev. side(A, B, P) = (bx - ax) * (py - ay) - (by - ay) * (px - ax). For line i < n_lines, prev the stored anchor
+ *      and p this frame's: a = side(A, B, prev), c = side(A, B, p), u = side(prev, p, A), v = side(prev, p, B). If any of the four is NaN there is
+ *      no crossing; otherwise there is one iff (a >= 0) != (c >= 0) and (u >= 0) != (v >= 0). The direction is 0 when c >= 0, else 1.
+ *      line_count[i][dir][bin] += 1, and a CROSS event is emitted;
+ *   4. zones, even-odd rule: for zone z < n_zones and its edge e with i = e, j = e ? e - 1 : nv - 1: if (yi > py) != (yj > py) and
+ *      px < (xj - xi) * (py - yi) / (yj - yi) + xi, toggle. The zones at or beyond n_zones hold nobody. For every z < 16, bit 0 -> 1:
+ *      entries[z][bin] += 1, enter_frame[z] = f, an ENTER event (the first observation of a track counts as such); bit 1 -> 0: exits[z][bin] += 1,
+ *      dwell = f - enter_frame[z], dwell_sum[z][bin] += dwell, dwell_max[z][bin] = max(dwell_max[z][bin], dwell), an EXIT event.
+ *      occupancy[z][bin] is rewritten every step as the number of observed tracks inside;
+ *   5. prev = p, has_prev = 1;
+ *   6. events are rows of eight int32 (kind, index, id, label, bin, frame, dwell, direction): kind DN_ZONE_CROSS / ENTER / EXIT / VANISH, index the
+ *      line or the zone, label the low 32 bits of T.label, dwell 0 for CROSS and ENTER, direction 0 except for CROSS. Their order is slot ascending,
+ *      and within a slot VANISH by zone, then CROSS by line, then EXIT / ENTER by zone;
+ *   7. the first max_events of a step are kept (events_out_dev [streams][max_events][8]); event_counts_out_dev [streams] is the kept number, the
+ *      excess is added to events_dropped, and the rows at or beyond the count are zero.
+ * The zone state, dn_zone_state_bytes(streams, max_tracks) bytes, 16-byte aligned: per stream W = 1156 + 22 Tp 4-byte words, Tp = max_tracks rounded
+ * up to a multiple of 4 as in the tracker, streams back to back. Words 0 .. 3: int32 events_dropped, three reserved (0). Then per-slot arrays of Tp
+ * entries each, in this order: int32 id, int32 bin, int32 has_prev, fp32 px, fp32 py, uint32 inside (bit z: zone z), int32 enter_frame [16][Tp].
+ * Then the counters: int32 line_count [16][2][8] (line, direction, bin); int32 entries, exits, vanished, occupancy, dwell_max [16][8] each (zone,
+ * bin); int64 dwell_sum [16][8]. dn_zone_reset is one launch: the streams b with which_dev[b] != 0 (NULL: all) become all zero; a new state must be
+ * reset before its first step.
+ * Limits: max_tracks 1 .. 256, max_events 1 .. 1024: DN_E_UNSUPPORTED above them (dn_zone_state_bytes then returns 0). DN_E_INVALID for null pointers
+ * (class_bin_dev and which_dev excepted), non-positive sizes (n_labels only with a class map), anchor not 0 or 1, track state / config / zone state /
+ * events not 16-byte aligned, event_counts not 4-byte aligned, or track_state_bytes below dn_track_state_bytes. DN_E_WORKSPACE for zstate_bytes below
+ * dn_zone_state_bytes. One workgroup per stream, one thread per slot, no workspace; integer counters meet through LDS integer atomics (an integer sum
+ * does not depend on the order), no float atomics; event positions come from a prefix scan inside the workgroup, so their order is fixed.
+ * Asynchronous on `stream`, no host synchronisation, can be captured; deterministic (the same bits on every run). */
+enum { DN_ZONE_CROSS = 1, DN_ZONE_ENTER = 2, DN_ZONE_EXIT = 3, DN_ZONE_VANISH = 4 };
+typedef struct dn_zone_config {     /* 2384 bytes; offsets: n_lines 0, lines 4, n_zones 260, nv 264, verts 328, reserved 2376 */
+    int32_t n_lines;                /* 0 .. 16 */
+    float lines[16][4];             /* (ax, ay, bx, by) */
+    int32_t n_zones;                /* 0 .. 16 */
+    int32_t nv[16];                 /* vertices per zone, 3 .. 16 */
+    float verts[16][16][2];         /* (x, y) */
+    int32_t reserved[2];            /* 0: keeps the records of an array 16-byte aligned */
+} dn_zone_config;
+DN_API size_t dn_zone_state_bytes(int streams, int max_tracks);
+DN_API int dn_zone_reset(void* zstate_dev, int streams, int max_tracks, const uint8_t* which_dev, void* stream);
+DN_API int dn_zone_update(const void* track_state_dev, size_t track_state_bytes, int streams, int max_tracks, const dn_zone_config* config_dev,
+                          const uint8_t* class_bin_dev, int n_labels, int anchor, void* zstate_dev, size_t zstate_bytes, int32_t* events_out_dev,
+                          int32_t* event_counts_out_dev, int max_events, void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
