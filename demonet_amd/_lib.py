@@ -62,6 +62,12 @@ class ZoneConfig(C.Structure):
                 ("verts", C.c_float * 2 * 16 * 16), ("reserved", C.c_int32 * 2)]
 
 
+class CropParams(C.Structure):
+    _fields_ = [("margin", C.c_float), ("square", C.c_int32), ("min_width", C.c_int32), ("min_height", C.c_int32),
+                ("mean", C.c_float * 3), ("std", C.c_float * 3), ("out_h", C.c_int32), ("out_w", C.c_int32), ("out_fp16", C.c_int32),
+                ("capacity", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("n_tensors", C.c_int32), ("n_ops", C.c_int32),
                 ("tensors", C.POINTER(TensorDesc)), ("ops", C.POINTER(OpDesc)),
@@ -147,6 +153,9 @@ _SIGNATURES = {
     "dn_zone_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dn_zone_update": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dn_crop_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "dn_crop_objects": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(CropParams),
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 # include/demonet_hip_debug.h: test support beside the boundary (not part of EXPORTS, which mirrors demonet_hip.h)

@@ -4,6 +4,7 @@
 // reference ops replaced: nn.MaxPool2d (ssd_vgg16.py:34-37,85), F.normalize * scale_weight (ssd_vgg16.py:101),
 //   F.interpolate(mode='bilinear', align_corners=False) (transform.py:52-53).
 #include "common.h"
+#include "frametap.h"
 
 namespace {
 
@@ -61,15 +62,6 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const half_t* __restrict__ 
         for (int e = 0; e < 8; ++e) o[e] = (half_t)((float)v[e] * inv * scale[c0 + e]);
         *reinterpret_cast<half8*>(out + (size_t)px * c + c0) = o;
     }
-}
-
-// one rounding per operation, no FMA contraction: the float and the uint8 input paths must produce the same resized image
-__device__ __forceinline__ float bilerp(float a, float b, float c, float d, float hx, float lx, float hy, float ly) {
-#pragma clang fp contract(off)
-    const float t0 = hx * a, t1 = lx * b, b0 = hx * c, b1 = lx * d;
-    const float top = t0 + t1, bot = b0 + b1;
-    const float u = hy * top, v = ly * bot;
-    return u + v;
 }
 
 __global__ __launch_bounds__(256) void resize_kernel(const float* __restrict__ in, float* __restrict__ out,
@@ -137,34 +129,7 @@ __global__ __launch_bounds__(256) void u8hwc_kernel(const unsigned char* __restr
 // DEVICE memory at run time, every image with its own planes, pitches and size. Each of the four bilinear taps is converted to 8-bit RGB in
 // integer arithmetic as it is read (1 luma + 2 chroma bytes; chroma sample (x >> 1, y >> 1)); from there on the arithmetic is u8hwc_kernel's,
 // expression for expression, so the block equals what u8hwc_kernel writes from the converted frame, bit for bit.
-struct FrameColor { int cy, crv, cbu, cgu, cgv, yo; };       // round(c * 2^14), the luma offset (frame_color below)
-
-__device__ __forceinline__ int frame_clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
-template <int FMT>
-__device__ __forceinline__ void frame_tap(const dn_frame& f, int x, int y, const FrameColor& k, float* rgb) {
-    int r, g, b;
-    if (FMT == DN_FRAME_RGB24 || FMT == DN_FRAME_BGR24) {
-        const uint8_t* p = f.plane[0] + (size_t)y * f.pitch[0] + (size_t)x * 3;
-        r = p[FMT == DN_FRAME_RGB24 ? 0 : 2]; g = p[1]; b = p[FMT == DN_FRAME_RGB24 ? 2 : 0];
-    } else {
-        const int yy = (int)f.plane[0][(size_t)y * f.pitch[0] + x] - k.yo;
-        int u, v;
-        if (FMT == DN_FRAME_NV12) {
-            const uint8_t* p = f.plane[1] + (size_t)(y >> 1) * f.pitch[1] + (size_t)(x >> 1) * 2;
-            u = (int)p[0] - 128; v = (int)p[1] - 128;
-        } else {
-            u = (int)f.plane[1][(size_t)(y >> 1) * f.pitch[1] + (x >> 1)] - 128;
-            v = (int)f.plane[2][(size_t)(y >> 1) * f.pitch[2] + (x >> 1)] - 128;
-        }
-        const int l = k.cy * yy + (1 << 13);
-        r = frame_clamp8((l + k.crv * v) >> 14);                    // >> of a signed int: arithmetic (floor)
-        g = frame_clamp8((l - k.cgu * u - k.cgv * v) >> 14);
-        b = frame_clamp8((l + k.cbu * u) >> 14);
-    }
-    rgb[0] = (float)r / 255.f; rgb[1] = (float)g / 255.f; rgb[2] = (float)b / 255.f;
-}
-
+// (FrameColor, frame_tap and bilerp: frametap.h, shared with crops.hip)
 template <int FMT>
 __global__ __launch_bounds__(256) void frames_kernel(const dn_frame* __restrict__ frames, float* __restrict__ out, float* __restrict__ scale_xy,
                                                      int n, int oh, int ow, FrameColor k) {
@@ -243,18 +208,6 @@ __global__ __launch_bounds__(256) void frame_regions_kernel(const dn_frame* __re
     frame_tap<FMT>(f, X1, Y1, k, d);
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c * plane] = bilerp(a[c], b[c], cc[c], d[c], hx, lx, hy, ly);
-}
-
-// round(c * 2^14) of cy = 255/219, crv = 2(1 - Kr) cs, cbu = 2(1 - Kb) cs, cgu = 2 Kb (1 - Kb) / Kg cs, cgv = 2 Kr (1 - Kr) / Kg cs with
-// cs = 255/224, yo = 16 (limited range) or cy = cs = 1, yo = 0 (full range); BT.601: Kr, Kb = 0.299, 0.114, BT.709: 0.2126, 0.0722
-// (tests/frames_ref.py derives the same integers from Kr, Kb in float64)
-bool frame_color(int color, FrameColor* k) {
-    const bool full = (color & DN_COLOR_FULL_RANGE) != 0;
-    switch (color & ~DN_COLOR_FULL_RANGE) {
-        case DN_COLOR_BT601: *k = full ? FrameColor{16384, 22970, 29032, 5638, 11700, 0} : FrameColor{19077, 26149, 33050, 6419, 13320, 16}; return true;
-        case DN_COLOR_BT709: *k = full ? FrameColor{16384, 25802, 30402, 3069, 7670, 0} : FrameColor{19077, 29372, 34610, 3494, 8731, 16}; return true;
-    }
-    return false;
 }
 
 }  // namespace

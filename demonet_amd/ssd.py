@@ -451,6 +451,16 @@ class SSD(_Tracked):
         from .sliced import track_sliced_frames
         return track_sliced_frames(self, batch, tracker, slicer, analytics)
 
+    def crop_objects(self, batch, cropper, boxes, counts, select=None):
+        """The objects of the frames as fixed-size normalised patches for a second model, on the device (demonet_amd/crops.py):
+        cropper(batch, boxes, counts, select) for a crops.ObjectCropper on this model's device. boxes and counts are a tracking step's or a
+        forward's, in frame pixels:
+            boxes, scores, labels, ids, det, counts, det_ids = model.track_sliced_frames(batch, tracker, slicer)
+            patches, index, totals = model.crop_objects(batch, cropper, boxes, counts)
+        Returns what the cropper returns; no device-to-host copy."""
+        from .crops import crop_objects
+        return crop_objects(self, batch, cropper, boxes, counts, select)
+
     def batch_split(self, n: int) -> int:
         """Number of parallel sub-batch launch chains a forward of n images is issued as (1 = a single chain)."""
         if self._handle is None:

@@ -702,6 +702,65 @@ DN_API int dn_zone_update(const void* track_state_dev, size_t track_state_bytes,
                           const uint8_t* class_bin_dev, int n_labels, int anchor, void* zstate_dev, size_t zstate_bytes, int32_t* events_out_dev,
                           int32_t* event_counts_out_dev, int max_events, void* stream);
 
+/* Object crops from video surfaces behind the tracker (csrc/crops.hip): the boxes of every stream become fixed-size normalised patches
+ * cut out of the frames at native resolution -- the input of a second model (a re-identification embedder, an attribute or plate classifier) --
+ * without the boxes visiting the host and without a converted frame. demonet_amd/crops.py (ObjectCropper) is the caller.
+ * frames_dev: [streams] dn_frame records as for dn_forward_frames (format, color: its codes); stream b reads frame b. boxes_dev: [streams][d][4] fp32
+ * (x1, y1, x2, y2) in that frame's pixels -- the tracker's boxes_out, or a forward's boxes. counts_dev: [streams] int32. select_dev: [streams][d]
+ * uint8 or NULL; a row whose byte is 0 is skipped (caller policies such as "every k-th frame of a track's life", computed on the device).
+ * params: HOST memory, read during the call only. All arithmetic is fp32 with one rounding per operation and no contraction, divisions correctly
+ * rounded.
+ * A step. For stream b, with W, H the size in the frame's record, the rows j < min(max(counts[b], 0), d) in ascending order:
+ *   1. (x1, y1, x2, y2) = boxes[b][j]. The row is a candidate iff select is NULL or select[b][j] != 0, all four coordinates are finite,
+ *      w = x2 - x1 > 0 and h = y2 - y1 > 0;
+ *   2. the margin: mx = w * margin, my = h * margin, xa = x1 - mx, xb = x2 + mx, ya = y1 - my, yb = y2 + my;
+ *   3. with `square`: cw = xb - xa, ch = yb - ya, s = fmaxf(cw, ch), hs = s * 0.5f, cx = (xa + xb) * 0.5f, cy = (ya + yb) * 0.5f,
+ *      xa = cx - hs, xb = cx + hs, ya = cy - hs, yb = cy + hs;
+ *   4. the row is dropped if any of xa, xb, ya, yb is not finite, or if the rectangle does not meet the frame: it must satisfy
+ *      xb > 0 && xa < (float)W && yb > 0 && ya < (float)H;
+ *   5. the integer rectangle, clamped in float first and then converted: X0 = (int)fminf(fmaxf(floorf(xa), 0), W - 1),
+ *      X1 = (int)fminf(fmaxf(ceilf(xb), X0 + 1), W), Y0 and Y1 likewise with ya, yb, H; width = X1 - X0, height = Y1 - Y0. The row is skipped if
+ *      width < min_width or height < min_height. (Frame 260 x 200, margin 0: the box (10.2, 20.7, 30.1, 40.0) gives (X0, Y0, width, height) =
+ *      (10, 20, 21, 20).) For a frame side above 2^24, where W - 1 is not exact in fp32, the integers are clamped once more to the same bounds;
+ *   6. the surviving rows are numbered s = 0, 1, ... in the order (stream ascending, row ascending). Rows with s < capacity are kept.
+ *      totals_out_dev = (kept, dropped, 0, 0) int32; dropped counts the survivors at or beyond capacity;
+ *   7. index_out_dev [capacity][8] int32: for every kept s the row (b, j, X0, Y0, width, height, 0, 0); the rows at or beyond kept are
+ *      (-1, 0, 0, 0, 0, 0, 0, 0);
+ *   8. patches_out_dev [capacity][3][out_h][out_w], NCHW, channels R, G, B, fp32 or fp16: for every kept s the value v at (c, oy, ox) is exactly
+ *      what dn_forward_regions computes for the region (b, X0, Y0, width, height, 0) at the output size out_h x out_w: the tap conversion of
+ *      dn_forward_frames, /255, the bilinear resize in REGION coordinates with the second tap clamped at the rectangle's edge, chroma sampled
+ *      in frame coordinates, and one tap with the same bits where the rectangle has exactly the patch size. The stored value is
+ *      o = (v - mean[c]) / std[c]: one subtraction, then one correctly rounded division (torchvision Normalize's order; no reciprocal, no fused
+ *      scale and bias). fp16 output is the round-to-nearest-even conversion of o.
+ *      PATCHES AT OR BEYOND kept ARE NOT WRITTEN: they keep whatever the memory held (zeroing 8192 unused slots would cost more than the work).
+ * Consequence: with mean = 0, std = 1 and fp32 output, patch s equals, bit for bit, what dn_forward_u8 computes as its network input from the
+ * rectangle cut out of the converted frame.
+ * TRUST BOUNDARY: the frame table is trusted as for dn_forward_frames. Box values are NOT: whatever bits boxes_dev, counts_dev and select_dev hold,
+ * no read leaves the frame, because step 5 clamps the rectangle against the record's own width and height and counts is clamped to 0 .. d.
+ * Limits: streams 1 .. 1024, d 1 .. 512, capacity 1 .. 8192, out_h and out_w 1 .. 1024, a known format and colour code (dn_forward_frames'):
+ * DN_E_UNSUPPORTED beyond them (dn_crop_workspace_bytes then returns 0). DN_E_INVALID for null pointers (select_dev excepted), non-positive sizes,
+ * a margin that is NaN, negative or infinite, a std that is not finite and positive, a mean that is not finite, square or out_fp16 not 0 or 1,
+ * min_width or min_height below 1, non-zero reserved words, boxes, patches, index, totals or the workspace not 16-byte aligned, counts not 4-byte
+ * aligned. DN_E_WORKSPACE for workspace_bytes below dn_crop_workspace_bytes(streams, d). Every error is raised before anything is launched.
+ * Two launches: one workgroup per stream runs steps 1-5 and numbers the stream's survivors with a prefix scan; capacity x row-band workgroups then
+ * find their slot's stream from the per-stream counts and write index, totals and patches. Asynchronous on `stream`, no host synchronisation, can
+ * be captured (all tables are read when the kernels run); no float atomics; deterministic (the same bits on every run). */
+typedef struct dn_crop_params {      /* 64 bytes, HOST memory, read during the call only */
+    float   margin;                  /* >= 0, finite: the box grows by margin * its width / height on each side */
+    int32_t square;                  /* 0 | 1: after the margin, grow the shorter side to the longer one about the centre */
+    int32_t min_width, min_height;   /* >= 1: rectangles smaller than this (after clamping to the frame) are skipped */
+    float   mean[3], std[3];         /* per channel R, G, B; std finite and > 0 */
+    int32_t out_h, out_w;            /* the patch size, 1 .. 1024 each */
+    int32_t out_fp16;                /* 0: fp32 patches, 1: fp16 (round to nearest even of the fp32 value) */
+    int32_t capacity;                /* patch slots, 1 .. 8192 */
+    int32_t reserved[2];             /* 0 */
+} dn_crop_params;
+DN_API size_t dn_crop_workspace_bytes(int streams, int d);
+DN_API int dn_crop_objects(const dn_frame* frames_dev, int format, int color,
+                           const float* boxes_dev, const int32_t* counts_dev, const uint8_t* select_dev, int streams, int d,
+                           const dn_crop_params* params, void* patches_out_dev, int32_t* index_out_dev, int32_t* totals_out_dev,
+                           void* workspace_dev, size_t workspace_bytes, void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
