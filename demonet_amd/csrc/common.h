@@ -348,6 +348,10 @@ struct ExpDwArgs {
     int stage_out = 0; FastDiv fd_oc8 = {1, 0};    // filled by the launcher: the projected tile leaves through LDS as row-contiguous 16-byte chunks
 };
 int launch_expdw(const ExpDwArgs& a, hipStream_t s);
+// expdw_direct.hip: the per-tap body of the 16 -> 64 -> cout stride-2 block. expdw_direct_band: output rows per band, 0 = not its shape (launch_expdw
+// then takes the bodies of expdw.hip); launch_expdw_direct enqueues it (the caller notes the launch's label).
+int expdw_direct_band(const ExpDwArgs& a);
+int launch_expdw_direct(const ExpDwArgs& a, int bh, hipStream_t s);
 int expdw_tiles_per_image(int Ho, int Wo, int stride);
 bool expdw_supported(int cin, int cexp, int k, int stride);
 bool expdw_project_supported(int cexp, int cout, int Ho, int Wo, int stride);

