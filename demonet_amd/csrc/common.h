@@ -352,6 +352,10 @@ int launch_expdw(const ExpDwArgs& a, hipStream_t s);
 // then takes the bodies of expdw.hip); launch_expdw_direct enqueues it (the caller notes the launch's label).
 int expdw_direct_band(const ExpDwArgs& a);
 int launch_expdw_direct(const ExpDwArgs& a, int bh, hipStream_t s);
+// expdw_rows.hip: the row-reuse body of the 24 -> 72 -> cout stride-1 block (a wave walks down a column strip and expands every input row once).
+// expdw_rows_band: output rows per band, 0 = not its shape; launch_expdw_rows enqueues it (the caller notes the launch's label).
+int expdw_rows_band(const ExpDwArgs& a);
+int launch_expdw_rows(const ExpDwArgs& a, int bh, hipStream_t s);
 int expdw_tiles_per_image(int Ho, int Wo, int stride);
 bool expdw_supported(int cin, int cexp, int k, int stride);
 bool expdw_project_supported(int cexp, int cout, int Ho, int Wo, int stride);

@@ -865,6 +865,15 @@ int launch_expdw(const ExpDwArgs& a0, hipStream_t s) {
             return launch_expdw_direct(a, bh, s);
         }
     }
+    // the row-reuse body (expdw_rows.hip) for the one-chunk stride-1 block 24 -> 72 -> cout, under the label of the body it replaces in the same way
+    if (!g_xd_stamps && dn_knob("DN_EXPDW_ROWS", 1)) {
+        const int bh = expdw_rows_band(a);
+        if (bh > 0) {
+            if (oh == 8 && ow == 16 && dn_knob("DN_EXPDW_PERSIST", 1)) dn_note_kernel("expdw_one_kernel<3,1,8,16,2>");
+            else dn_note_kernel("expdw_kernel<3,1,%d,%d,2,true,true>", oh, ow);
+            return launch_expdw_rows(a, bh, s);
+        }
+    }
     if (a.k == 3 && a.stride == 1) return launch_ks<3, 1>(a, oh, ow, s);
     if (a.k == 3 && a.stride == 2) return launch_ks<3, 2>(a, oh, ow, s);
     if (a.k == 5 && a.stride == 1) return launch_ks<5, 1>(a, oh, ow, s);

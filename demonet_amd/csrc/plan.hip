@@ -1795,7 +1795,7 @@ void depthwise_debug_limits(const DwArgs& a, int tw, bool* in_range, size_t* wld
 //   "headfuse"  n H W C nc0 nc1 stride0 stride1                                 -> head_fused_level_supported (supported=)
 //   "headpost"  n H W aloc K A                                                  -> head_fused_post_supported of one level with the epilogue (supported=)
 //   "patch_blocks" n h w                                                        -> conv_patch_resident_blocks (blocks=, launched=: below the launcher's 2^30)
-//   "expdw"     n h w cin cexp cout k stride act1 act2 has_res pool             -> expdw_direct_band (body=direct / tiled, band=)
+//   "expdw"     n h w cin cexp cout k stride act1 act2 has_res pool             -> expdw_direct_band / expdw_rows_band (body=direct / rows / tiled, band=)
 extern "C" __attribute__((visibility("default"))) int dn_debug_choice(const char* family, const int64_t* d, int nd, char* buf, int capacity) {
     DN_REQUIRE(family && d && buf && capacity > 0, "dn_debug_choice: null argument");
     static const half_t dummy_h[8] = {};
@@ -1900,7 +1900,8 @@ extern "C" __attribute__((visibility("default"))) int dn_debug_choice(const char
         a.pad = (a.k - 1) / 2; a.Ho = (a.H + 2 * a.pad - a.k) / a.stride + 1; a.Wo = (a.W + 2 * a.pad - a.k) / a.stride + 1;
         a.act1 = (int)d[8]; a.act2 = (int)d[9]; a.has_res = (int)d[10]; a.xq = xcd_images_per_group(a.n);
         const int bh = dn_knob("DN_EXPDW_DIRECT", 1) ? expdw_direct_band(a) : 0;
-        snprintf(buf, (size_t)capacity, "body=%s band=%d", bh > 0 ? "direct" : "tiled", bh);
+        const int rb = bh == 0 && dn_knob("DN_EXPDW_ROWS", 1) ? expdw_rows_band(a) : 0;
+        snprintf(buf, (size_t)capacity, "body=%s band=%d", bh > 0 ? "direct" : (rb > 0 ? "rows" : "tiled"), bh > 0 ? bh : rb);
         return DN_OK;
     }
     dn_set_error("dn_debug_choice: unknown family '%s'", family);

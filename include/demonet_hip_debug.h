@@ -52,7 +52,8 @@ DN_API int dn_debug_stem(const float* img_dev, const float* w_dev, const float* 
  *   "headpost"  n H W anchors_per_location K A                      (supported=: the level's workgroups may run the softmax / decode epilogue)
  *   "patch_blocks" n h w        (blocks=: 16 x 16 blocks of a conv_patch_resident_kernel launch; launched=: below the launcher's limit)
  *   "expdw"     n h w cin cexp cout k stride act1 act2 has_res pool     (body=direct: the per-tap body of expdw_direct.hip takes the launch,
- *               band= its output rows per workgroup; body=tiled: the bodies of expdw.hip; reads DN_EXPDW_DIRECT / DN_EXPDW_DIRECT_BAND)
+ *               band= its output rows per workgroup; body=rows: the row-reuse body of expdw_rows.hip, band= its output rows per wave; body=tiled:
+ *               the bodies of expdw.hip; reads DN_EXPDW_DIRECT / DN_EXPDW_DIRECT_BAND / DN_EXPDW_ROWS / DN_EXPDW_ROWS_BAND)
  * 0 on success. */
 DN_API int dn_debug_choice(const char* family, const int64_t* dims, int ndims, char* buf, int capacity);
 
