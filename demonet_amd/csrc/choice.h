@@ -1,4 +1,4 @@
-// Which kernel a 1x1 convolution, a dense convolution, a grouped head launch, a depthwise convolution, the squeeze-excitation FCs, a stem or the soft-NMS reduce runs on: ONE pure function per family (no HIP call, no label, argument
+// Which kernel a 1x1 convolution, a dense convolution, a grouped head launch, a depthwise convolution, the squeeze-excitation FCs, a stem, the soft-NMS reduce or a fused inverted-residual block runs on: ONE pure function per family (no HIP call, no label, argument
 // untouched; knobs read through dn_knob at the call -- INTEGRATION.md: kernel-choice knobs at every launch). The launchers validate, ask here and switch from
 // the answer to the template instantiation; the plan-time predicates ask the same functions about a shape. The order of the rules in a function is their
 // precedence, with the measurement that justifies a rule next to it; capability tests (*_shape, *_supported) stand in front of the function that uses them.
@@ -412,6 +412,126 @@ constexpr int post_nw_bucket(int topk) {
 // The soft reduce has one form: four waves with an LDS exchange per step (one wave, no exchange, for a capacity of 64 candidates). Measured
 // against one wave holding NW candidates per lane (no barrier) at topk 300, batch 64, 90 classes: 1.53 vs 2.05 ms per forward in linear mode,
 // 1.42 vs 1.98 ms in Gaussian mode; the one-wave form is gone.
+
+// ================================================================ (h) the fused inverted-residual launch (expdw.hip; its two other bodies in expdw_direct.hip, expdw_rows.hip)
+constexpr int EXPDW_NT = 512;           // threads per workgroup: 8 waves (expdw.hip asserts its own constants against these three)
+constexpr int EXPDW_EW = 72;            // halfs per row of the expanded tile in LDS: a 64-channel chunk + 8, which a last chunk of exactly 72 channels fills
+constexpr int EXPDW_XKS = 8;            // most full 16-deep K steps of the expand (cin <= 128)
+constexpr size_t EXPDW_LDS_MAX = 160 * 1024, EXPDW_PERSIST_LDS_MAX = 80 * 1024;     // a workgroup's LDS; the persistent form's (two resident workgroups per CU)
+constexpr int EXPDW_MIN_WGS = 1024;     // (without a project stage) split the chunks over grid.y until there are enough workgroups to fill the chip a few times over
+
+struct ExpDwChoice {
+    enum Body {
+        NONE,               // the tiled bodies cannot take the launch (lds beyond EXPDW_LDS_MAX, or a grid beyond 65535 in y or z) and no other body does
+        DIRECT, ROWS,       // expdw_direct_kernel<act1> (expdw_direct.hip), expdw_rows_kernel<act1> (expdw_rows.hip): bands of `band` output rows
+        ONE_PERSIST,        // expdw_one_kernel<k, stride, oh, ow, ksm, xw8, wide>: the resident workgroups walk the tiles
+        TILED               // expdw_kernel<k, stride, oh, ow, ksm, exp, proj, xw8, wide, one>: one workgroup per tile (and run of chunks)
+    };
+    Body body = NONE;
+    int k = 0, stride = 0, oh = 0, ow = 0;              // kernel size, stride, output tile
+    int ksm = 0, xw8 = 0;                               // full K steps of the expand held in registers; X row width in 16-byte pieces where it is a compile-time constant (0: runtime)
+    bool exp = false, proj = false, wide = false, one = false;   // expand / project stage; a last chunk of 72 channels taken whole; the chunk loop is one chunk
+    int band = 0;                                       // DIRECT, ROWS: output rows per band
+    int cpw = 0, zsplit = 1, xw = 0, stage_out = 0;     // chunks per workgroup and their split over grid.y; halfs per X row; the projected tile leaves through LDS
+    size_t lds = 0, lds_p = 0;                          // LDS bytes of expdw_kernel / of expdw_one_kernel (+ the tile's own output buffer)
+    char label[64] = "";                                // the launch's label: ALWAYS the tiled choice's, whichever body runs (plan signatures and bench families do not see DIRECT / ROWS)
+};
+
+// the output tile of a map
+inline void expdw_tile(int Ho, int Wo, int stride, int proj_cout, int* oh, int* ow) {
+    if (Wo <= 5 && Ho <= 5) { *oh = 5; *ow = 5; }
+    else if (Wo <= 10) { *oh = 5; *ow = 10; }
+    else if (Wo < 32 && Wo % 16 != 0) {                     // 19x19 / 20x20 maps: 10-wide tiles waste nothing
+        if (stride == 1) { *oh = 10; *ow = 10; } else { *oh = 5; *ow = 10; }       // (measured again in round 4 on the V2 model at 300 x 300: 5 x 10 tiles there are 2.4 % slower, although the 10 x 10 variants with cin >= 64 spill 36 - 44 B per lane)
+        // with a project stage the (pixel tile x channel tile) units must fit the 8 waves: 100 pixels x 80 channels = 12 units, 50 x 80 = 6
+        if (proj_cout > 0 && ((*oh * *ow + 31) / 32) * ((proj_cout + 31) / 32) > EXPDW_NT / 64) { *oh = 5; *ow = 10; }
+    }
+    else { *oh = 8; *ow = (stride == 1) ? 16 : 8; }
+}
+inline int expdw_tiles_per_image(int Ho, int Wo, int stride) {
+    int oh, ow;
+    expdw_tile(Ho, Wo, stride, 0, &oh, &ow);
+    return dn_cdiv(Ho, oh) * dn_cdiv(Wo, ow);
+}
+inline bool expdw_supported(int cin, int cexp, int k, int stride) {
+    return cin % 8 == 0 && cin <= 16 * EXPDW_XKS && cexp % 8 == 0 && (k == 3 || k == 5) && (stride == 1 || stride == 2);
+}
+// the project stage keeps one MFMA accumulator per wave: (pixels of the tile / 32) x (cout / 32) units must fit the 8 waves
+inline bool expdw_project_supported(int cexp, int cout, int Ho, int Wo, int stride) {
+    int oh, ow;
+    expdw_tile(Ho, Wo, stride, cout, &oh, &ow);
+    return cexp % 8 == 0 && cout % 8 == 0 && ((oh * ow + 31) / 32) * ((cout + 31) / 32) <= EXPDW_NT / 64;
+}
+// rows of the staged input region of a tile, in whole 32-row MFMA tiles (ExpDwGeom::ROWS)
+constexpr int expdw_region_rows(int k, int stride, int oh, int ow) { return (((oh - 1) * stride + k) * ((ow - 1) * stride + k) + 31) / 32 * 32; }
+// the persistent single-chunk form (expdw_one_kernel) is instantiated for the block shapes that take it: 3x3 on the 8 x 8 stride-2 / 8 x 16 stride-1 tiles of
+// the large maps, cin 16 / 24 / 32. It needs the staged output tile inside the dead E buffer (no barrier between the project stage and its write), a stride of
+// whole tiles per step, and no pooled sums or stamps.
+inline bool expdw_persist_supported(const ExpDwArgs& a, const ExpDwChoice& c, bool stamped) {
+    return c.exp && c.proj && c.ksm <= 2 && (c.xw8 == 3 || c.xw8 == 5) && c.k == 3 && c.oh == 8 && c.ow == (c.stride == 1 ? 16 : 8) && !a.pool && !stamped &&
+           a.cout % 8 == 0 && a.cout <= 256 && c.lds_p <= EXPDW_PERSIST_LDS_MAX && fd_ok((unsigned long long)c.oh * c.ow * (a.cout >> 3), (unsigned)(a.cout >> 3));
+}
+
+// `a` as launch_expdw has validated it (its DN_REQUIREs; the launcher-filled fields are not read). stamped: a dev build with phase stamps armed
+// (dn_debug_expdw_stamps) -- it takes neither the persistent form nor the two other bodies.
+inline ExpDwChoice expdw_choose(const ExpDwArgs& a, bool stamped) {
+    ExpDwChoice c;
+    c.k = a.k; c.stride = a.stride; c.exp = a.w1 != nullptr; c.proj = a.w3 != nullptr;
+    c.xw = ((a.cin + 15) / 16) * 16 + 8;                    // round16(cin) + 8
+    expdw_tile(a.Ho, a.Wo, a.stride, c.proj ? a.cout : 0, &c.oh, &c.ow);
+    // The A fragments of the expand live in registers: 2 full K steps + the tail/bias step cover cin <= 40 (fewer registers -> more waves), then 5 (cin <= 88), 6
+    // (cin 96, with a project stage) or all 8. The block shapes of the backbones get compile-time X row widths: cin 8 / 16 (24 halfs; with a project stage),
+    // 24 / 32 (40), 40 (56), 80 (88: the 20 x 20 blocks and the squeeze-excitation blocks of the 20 x 20 / 10 x 10 maps), 96 (104; with a project stage).
+    // (cin 48 has 56-half rows too and takes that rung, as it always has, although it has three full K steps: no model has that width.)
+    if (!c.exp) { c.ksm = 2; c.xw8 = 0; }
+    else if (c.xw == 24) { c.ksm = 2; c.xw8 = c.proj ? 3 : 0; }
+    else if (c.xw == 40) { c.ksm = 2; c.xw8 = 5; }
+    else if (c.xw == 56) { c.ksm = 2; c.xw8 = 7; }
+    else if (c.xw == 88) { c.ksm = 5; c.xw8 = 11; }
+    else if (c.proj && a.cin <= 88) { c.ksm = 5; c.xw8 = 0; }
+    else if (c.proj && c.xw == 104) { c.ksm = 6; c.xw8 = 13; }
+    else { c.ksm = EXPDW_XKS; c.xw8 = 0; }
+    // LDS of expdw_kernel: X rows (+ 8 zero halfs), the E tile, the chunk's depthwise weights, the depthwise output (project only); depthwise bias, pooled-sum
+    // scratch, project bias
+    const int rows = expdw_region_rows(a.k, a.stride, c.oh, c.ow), drows = (c.oh * c.ow + 31) / 32 * 32, kk = a.k * a.k;
+    c.lds = ((size_t)rows * c.xw + 8 + (c.exp ? (size_t)rows * EXPDW_EW : 0) + kk * EXPDW_EW + (c.proj ? (size_t)drows * EXPDW_EW : 0)) * sizeof(half_t) +
+            (EXPDW_EW + EXPDW_NT / 64 * 64 + (c.proj ? 256 : 0)) * sizeof(float);
+    c.lds_p = c.lds + (size_t)c.oh * c.ow * a.cout * sizeof(half_t);
+    // chunks per workgroup (not split with a project stage: it sums over all chunks inside the workgroup)
+    const int tiles_y = dn_cdiv(a.Ho, c.oh), tiles = dn_cdiv(a.Wo, c.ow) * tiles_y, chunks = dn_cdiv(a.cexp, 64);
+    c.cpw = chunks;
+    while (!c.proj && c.cpw > 1 && (long)tiles * a.n * dn_cdiv(chunks, c.cpw) < EXPDW_MIN_WGS) --c.cpw;
+    c.zsplit = dn_cdiv(chunks, c.cpw);
+    if (c.proj) {
+        // the output tile is staged over the E .. depthwise-output buffers (everything between the X rows and the project bias)
+        const size_t avail = ((c.exp ? (size_t)rows * EXPDW_EW : 0) + kk * EXPDW_EW + (size_t)drows * EXPDW_EW) * sizeof(half_t) + (EXPDW_EW + EXPDW_NT / 64 * 64) * sizeof(float);
+        c.stage_out = (size_t)c.oh * c.ow * a.cout * sizeof(half_t) <= avail && a.cout % 8 == 0 && fd_ok((unsigned long long)c.oh * c.ow * (a.cout >> 3), (unsigned)(a.cout >> 3));
+    }
+    // The whole expanded width as ONE chunk (full blocks with at most two K steps): the chunk loop is not a loop. The wide variant (a last chunk of 72 channels
+    // taken whole) exists for the one shape that uses it: the whole expanded width IS that chunk (24 -> 72 -> 24). As a tail of a longer chunk run (cexp = 136,
+    // 200 ... with cin <= 40) it was never dispatched by the model zoo and every such instantiation spilled 36 - 76 B per lane at the 128-register cap: not
+    // instantiated.
+    const bool full = c.exp && c.proj && c.ksm <= 2, one_knob = dn_knob("DN_EXPDW_ONE", 1) != 0;
+    c.wide = full && a.cexp == EXPDW_EW && one_knob;
+    const bool one_chunk = full && (c.wide || a.cexp <= 64);
+    // ... walked by the resident workgroups (DN_EXPDW_PERSIST), else by one workgroup per tile (DN_EXPDW_ONE; 0: the chunk loop's general form, 72 channels as 64 + 8)
+    const bool persist = one_chunk && expdw_persist_supported(a, c, stamped) && dn_knob("DN_EXPDW_PERSIST", 1);
+    c.one = one_chunk && (persist || one_knob);
+    const bool fits = c.lds <= EXPDW_LDS_MAX && (long)tiles_y * c.zsplit <= 65535 && a.n <= 65535 && (c.exp || c.proj) &&
+                      (!c.proj || (drows / 32) * dn_cdiv(a.cout, 32) <= EXPDW_NT / 64);
+    c.body = !fits ? ExpDwChoice::NONE : persist ? ExpDwChoice::ONE_PERSIST : ExpDwChoice::TILED;
+    if (persist) snprintf(c.label, sizeof c.label, "expdw_one_kernel<%d,%d,%d,%d,%d>", c.k, c.stride, c.oh, c.ow, c.ksm);
+    else snprintf(c.label, sizeof c.label, "expdw_kernel<%d,%d,%d,%d,%d,%s,%s>", c.k, c.stride, c.oh, c.ow, c.ksm, c.exp ? "true" : "false", c.proj ? "true" : "false");
+    // The two other bodies replace body and band, never the label. The per-tap body for the one-chunk stride-2 block 16 -> 64 -> cout, then the row-reuse body
+    // for the one-chunk stride-1 block 24 -> 72 -> cout; *_band: output rows per band, 0 = not that body's shape.
+    if (!stamped && dn_knob("DN_EXPDW_DIRECT", 1)) {
+        if (const int bh = expdw_direct_band(a)) { c.body = ExpDwChoice::DIRECT; c.band = bh; return c; }
+    }
+    if (!stamped && dn_knob("DN_EXPDW_ROWS", 1)) {
+        if (const int bh = expdw_rows_band(a)) { c.body = ExpDwChoice::ROWS; c.band = bh; return c; }
+    }
+    return c;
+}
 
 // ================================================================ a request that the chosen kernel does not implement is an error, not a launch
 inline int pw_check_honoured(const PwArgs& a, const PwChoice& c, const char* who) {

@@ -342,23 +342,22 @@ struct ExpDwArgs {
     const half_t* wd; const float* bd;             // depthwise [k*k][cexp]
     const half_t* w3; const float* b3;             // project [cout][cexp]; null: stop after the depthwise stage (out has cexp channels)
     int n, H, W, Ho, Wo, cin, cexp, cout, k, stride, pad, act1, act2, has_res;   // has_res: out += x (stride 1, cout == cin)
-    int xw, chunks_per_wg;                         // filled by the launcher
+    int xw, chunks_per_wg;                         // filled by the launcher, like stamps, stage_out and fd_oc8, from expdw_choose's answer (choice.h)
     int xq;                                        // XCD grouping: images per group (0: plain mapping)
     long long* stamps;                             // dev-only
-    int stage_out = 0; FastDiv fd_oc8 = {1, 0};    // filled by the launcher: the projected tile leaves through LDS as row-contiguous 16-byte chunks
+    int stage_out = 0; FastDiv fd_oc8 = {1, 0};    // the projected tile leaves through LDS as row-contiguous 16-byte chunks
 };
+// Which body a launch takes is decided by expdw_choose (choice.h, with the plan-time predicates expdw_tiles_per_image, expdw_supported and
+// expdw_project_supported) and nowhere else; launch_expdw validates, asks it, notes its label and launches.
 int launch_expdw(const ExpDwArgs& a, hipStream_t s);
-// expdw_direct.hip: the per-tap body of the 16 -> 64 -> cout stride-2 block. expdw_direct_band: output rows per band, 0 = not its shape (launch_expdw
-// then takes the bodies of expdw.hip); launch_expdw_direct enqueues it (the caller notes the launch's label).
+// expdw_direct.hip: the per-tap body of the 16 -> 64 -> cout stride-2 block. expdw_direct_band: its capability test -- output rows per band, 0 = not its
+// shape; launch_expdw_direct enqueues it.
 int expdw_direct_band(const ExpDwArgs& a);
 int launch_expdw_direct(const ExpDwArgs& a, int bh, hipStream_t s);
 // expdw_rows.hip: the row-reuse body of the 24 -> 72 -> cout stride-1 block (a wave walks down a column strip and expands every input row once).
-// expdw_rows_band: output rows per band, 0 = not its shape; launch_expdw_rows enqueues it (the caller notes the launch's label).
+// expdw_rows_band: its capability test -- output rows per band, 0 = not its shape; launch_expdw_rows enqueues it.
 int expdw_rows_band(const ExpDwArgs& a);
 int launch_expdw_rows(const ExpDwArgs& a, int bh, hipStream_t s);
-int expdw_tiles_per_image(int Ho, int Wo, int stride);
-bool expdw_supported(int cin, int cexp, int k, int stride);
-bool expdw_project_supported(int cexp, int cout, int Ho, int Wo, int stride);
 
 
 // Pyramid levels of the anchor axis. The class-major score array of the post-process is stored ANCHOR-MAJOR WITHIN A LEVEL:

@@ -18,7 +18,7 @@
 #include <stdlib.h>
 #include <algorithm>
 
-#include "common.h"
+#include "choice.h"
 
 #ifdef DN_DEV_STAMPS
 static long long* g_xd_stamps = nullptr;     // dev build only (tools/probe_expdw.py): per-workgroup phase stamps
@@ -40,6 +40,7 @@ constexpr int EW = 72;          // halfs per E row in LDS: 64 channels + 8 pad (
                                 // exactly 72 channels (the 24 -> 72 -> 24 block) is taken whole, columns 64..71 holding its last 8 channels
 constexpr int XKS = 8;          // max full 16-deep K steps of the expand (cin <= 128)
 constexpr int NT = 512;         // threads per workgroup: 8 waves; two workgroups per CU give 4 waves per SIMD to hide LDS/L2 latency
+static_assert(EW == EXPDW_EW && XKS == EXPDW_XKS && NT == EXPDW_NT, "expdw_choose (choice.h) sizes tiles, LDS and K steps with these");
 
 template <int K, int S, int OH, int OW>
 struct ExpDwGeom {
@@ -699,149 +700,83 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     store_prev();
 }
 
-template <int K, int S, int OH, int OW, int KSM, bool EXP, bool PROJ, int XW8, bool WD>
-int launch_kw(const ExpDwArgs& a, int tiles_x, int tiles_y, int zsplit, size_t lds, hipStream_t s) {
-    const dim3 grid(a.xq > 0 ? 8 * tiles_x : tiles_x, tiles_y * zsplit, a.xq > 0 ? a.xq : a.n);
-    // (instantiated for the block shapes that take it: 3x3 on the 8 x 8 stride-2 / 8 x 16 stride-1 tiles of the large maps, cin 16 / 24 / 32)
-    if constexpr (PROJ && EXP && KSM <= 2 && (XW8 == 3 || XW8 == 5) && K == 3 && OH == 8 && OW == (S == 1 ? 16 : 8)) {
-        // persistent single-chunk form: the workgroups that are resident (two per CU) walk the tiles. Needs the staged output tile inside the dead E
-        // buffer (no barrier between the project stage and its write) and a stride of whole tiles per step.
-        const size_t lds_p = lds + (size_t)OH * OW * a.cout * sizeof(half_t);        // + the tile's own output buffer
-        if ((WD ? a.cexp == EW : a.cexp <= 64) && !a.pool && !a.stamps && a.cout % 8 == 0 && a.cout <= 256 && lds_p <= 80 * 1024 &&
-            fd_ok((unsigned long long)OH * OW * (a.cout >> 3), (unsigned)(a.cout >> 3)) && dn_knob("DN_EXPDW_PERSIST", 1)) {
-            const int tiles = tiles_x * tiles_y;
-            const int groups = a.xq > 0 ? 8 : 1;
-            const long per_group = (long)(a.xq > 0 ? a.xq : a.n) * tiles;
-            const int wpg = (int)std::min<long>(per_group, 512 / groups);       // two resident workgroups per CU
-            DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(expdw_one_kernel<K, S, OH, OW, KSM, XW8, WD>)));
-            dn_note_kernel("expdw_one_kernel<%d,%d,%d,%d,%d>", K, S, OH, OW, KSM);
-            ExpDwArgs b = a;
-            b.fd_oc8 = fastdiv((unsigned)(a.cout >> 3));
-            hipLaunchKernelGGL((expdw_one_kernel<K, S, OH, OW, KSM, XW8, WD>), dim3(groups * wpg), dim3(NT), lds_p, s, b, tiles_x, tiles_y, wpg, wpg / tiles_x, wpg % tiles_x);
-            return DN_OK;
-        }
-    }
-    if constexpr (PROJ && EXP && KSM <= 2) {
-        if ((WD ? a.cexp == EW : a.cexp <= 64) && dn_knob("DN_EXPDW_ONE", 1)) {          // the whole expanded width is one chunk (72 channels: the wide variant)
-            DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(expdw_kernel<K, S, OH, OW, KSM, EXP, PROJ, XW8, WD, true>)));
-            dn_note_kernel("expdw_kernel<%d,%d,%d,%d,%d,%s,%s>", K, S, OH, OW, KSM, EXP ? "true" : "false", PROJ ? "true" : "false");
-            hipLaunchKernelGGL((expdw_kernel<K, S, OH, OW, KSM, EXP, PROJ, XW8, WD, true>), grid, dim3(NT), lds, s, a, tiles_x, tiles_y, zsplit);
-            return DN_OK;
-        }
-    }
-    if constexpr (WD) {
-        return DN_E_UNSUPPORTED;        // (launch_k only picks the wide variant together with the single-chunk form)
-    } else {
-        DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(expdw_kernel<K, S, OH, OW, KSM, EXP, PROJ, XW8, WD>)));
-        dn_note_kernel("expdw_kernel<%d,%d,%d,%d,%d,%s,%s>", K, S, OH, OW, KSM, EXP ? "true" : "false", PROJ ? "true" : "false");
-        hipLaunchKernelGGL((expdw_kernel<K, S, OH, OW, KSM, EXP, PROJ, XW8, WD>), grid, dim3(NT), lds, s, a, tiles_x, tiles_y, zsplit);
-        return DN_OK;
-    }
+// ---- host: from expdw_choose's answer (choice.h) to the instantiation. Nothing below decides: no knob, no shape test other than equality on the choice's
+// fields, no label. A combination that expdw_choose cannot produce is not instantiated and ends in no_instantiation.
+int no_instantiation(const ExpDwChoice& c) {
+    dn_set_error("expand+depthwise: no instantiation for %s (body %d, xw8 %d, wide %d, one %d)", c.label, (int)c.body, c.xw8, (int)c.wide, (int)c.one);
+    return DN_E_UNSUPPORTED;
 }
+
+template <int K, int S, int OH, int OW, int KSM, bool EXP, bool PROJ, int XW8, bool WD, bool ONE>
+int launch_tiled(const ExpDwArgs& a, const ExpDwChoice& c, hipStream_t s) {
+    static_assert(ExpDwGeom<K, S, OH, OW>::ROWS == expdw_region_rows(K, S, OH, OW), "choice.h sizes the LDS of this geometry");
+    const int tiles_x = dn_cdiv(a.Wo, OW), tiles_y = dn_cdiv(a.Ho, OH);
+    const dim3 grid(a.xq > 0 ? 8 * tiles_x : tiles_x, tiles_y * c.zsplit, a.xq > 0 ? a.xq : a.n);
+    DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(expdw_kernel<K, S, OH, OW, KSM, EXP, PROJ, XW8, WD, ONE>)));
+    hipLaunchKernelGGL((expdw_kernel<K, S, OH, OW, KSM, EXP, PROJ, XW8, WD, ONE>), grid, dim3(NT), c.lds, s, a, tiles_x, tiles_y, c.zsplit);
+    return DN_OK;
+}
+// the workgroups that are resident (two per CU) walk the tiles
+template <int K, int S, int OH, int OW, int KSM, int XW8, bool WD>
+int launch_persistent(const ExpDwArgs& a, const ExpDwChoice& c, hipStream_t s) {
+    const int tiles_x = dn_cdiv(a.Wo, OW), tiles_y = dn_cdiv(a.Ho, OH), tiles = tiles_x * tiles_y;
+    const int groups = a.xq > 0 ? 8 : 1;
+    const long per_group = (long)(a.xq > 0 ? a.xq : a.n) * tiles;
+    const int wpg = (int)std::min<long>(per_group, 512 / groups);       // two resident workgroups per CU
+    DN_HIP_CHECK(dn_allow_big_lds(reinterpret_cast<const void*>(expdw_one_kernel<K, S, OH, OW, KSM, XW8, WD>)));
+    hipLaunchKernelGGL((expdw_one_kernel<K, S, OH, OW, KSM, XW8, WD>), dim3(groups * wpg), dim3(NT), c.lds_p, s, a, tiles_x, tiles_y, wpg, wpg / tiles_x, wpg % tiles_x);
+    return DN_OK;
+}
+
+// wide, one and the persistent form exist for the full blocks with at most two K steps; the persistent form for the 3x3 blocks on the tiles of the large maps
 template <int K, int S, int OH, int OW, int KSM, bool EXP, bool PROJ, int XW8>
-int launch_k(const ExpDwArgs& a, int tiles_x, int tiles_y, int zsplit, size_t lds, hipStream_t s) {
+int launch_form(const ExpDwArgs& a, const ExpDwChoice& c, hipStream_t s) {
     if constexpr (PROJ && EXP && KSM <= 2) {
-        // the wide variant (a last chunk of 72 channels taken whole) exists for the one shape that uses it: the whole expanded width IS that chunk
-        // (24 -> 72 -> 24). As a tail of a longer chunk run (cexp = 136, 200 ... with cin <= 40) it was never dispatched by the model zoo and every
-        // such instantiation spilled 36 - 76 B per lane at the 128-register cap: not instantiated any more.
-        if (a.cexp == EW && dn_knob("DN_EXPDW_ONE", 1)) return launch_kw<K, S, OH, OW, KSM, EXP, PROJ, XW8, true>(a, tiles_x, tiles_y, zsplit, lds, s);
+        if constexpr ((XW8 == 3 || XW8 == 5) && K == 3 && OH == 8 && OW == (S == 1 ? 16 : 8)) {
+            if (c.body == ExpDwChoice::ONE_PERSIST)
+                return c.wide ? launch_persistent<K, S, OH, OW, KSM, XW8, true>(a, c, s) : launch_persistent<K, S, OH, OW, KSM, XW8, false>(a, c, s);
+        }
+        if (c.body == ExpDwChoice::TILED && c.wide && c.one) return launch_tiled<K, S, OH, OW, KSM, EXP, PROJ, XW8, true, true>(a, c, s);
+        if (c.body == ExpDwChoice::TILED && !c.wide && c.one) return launch_tiled<K, S, OH, OW, KSM, EXP, PROJ, XW8, false, true>(a, c, s);
     }
-    return launch_kw<K, S, OH, OW, KSM, EXP, PROJ, XW8, false>(a, tiles_x, tiles_y, zsplit, lds, s);
+    if (c.body == ExpDwChoice::TILED && !c.wide && !c.one) return launch_tiled<K, S, OH, OW, KSM, EXP, PROJ, XW8, false, false>(a, c, s);
+    return no_instantiation(c);
 }
 
 template <int K, int S, int OH, int OW>
-int launch_t(const ExpDwArgs& a0, hipStream_t s) {
-    using G = ExpDwGeom<K, S, OH, OW>;
-    ExpDwArgs a = a0;
-    const bool proj = a.w3 != nullptr, exp = a.w1 != nullptr;
-    constexpr int DROWS = (OH * OW + 31) / 32 * 32;
-    const size_t lds0 = ((size_t)G::ROWS * a.xw + 8 + (exp ? (size_t)G::ROWS * EW : 0) + K * K * EW + (proj ? (size_t)DROWS * EW : 0)) * sizeof(half_t) +
-                       (EW + NT / 64 * 64 + (proj ? 256 : 0)) * sizeof(float);
-    const size_t lds = lds0;
-    DN_REQUIRE(lds0 <= 160 * 1024, "expand+depthwise: LDS %zu B exceeds 160 KB", lds0);
-    // split the 64-channel chunks over grid.y until there are enough workgroups to fill the chip a few times over
-    // (not with a project stage: it sums over all chunks inside the workgroup)
-    const int tiles_x = dn_cdiv(a.Wo, OW), tiles_y = dn_cdiv(a.Ho, OH), tiles = tiles_x * tiles_y, chunks = dn_cdiv(a.cexp, 64);
-    const int min_wgs = 1024;
-    int cpw = chunks;
-    while (!proj && cpw > 1 && (long)tiles * a.n * dn_cdiv(chunks, cpw) < min_wgs) --cpw;
-    a.chunks_per_wg = cpw;
-    {   // dev: DN_EXPDW_STAMP_SEL = 10 * H + stride stamps only the launches of that shape (every launch writes the same buffer)
-        const int sel = g_xd_stamps ? dn_knob("DN_EXPDW_STAMP_SEL", 0) : 0;
-        a.stamps = (sel == 0 || sel == 10 * a.H + S) ? g_xd_stamps : nullptr;
-    }
-    if (proj) {
-        // the output tile is staged over the E .. depthwise-output buffers (everything between the X rows and the project bias)
-        const size_t avail = ((exp ? (size_t)G::ROWS * EW : 0) + K * K * EW + (size_t)DROWS * EW) * sizeof(half_t) + (EW + NT / 64 * 64) * sizeof(float);
-        a.stage_out = (size_t)OH * OW * a.cout * sizeof(half_t) <= avail && a.cout % 8 == 0 &&
-                      fd_ok((unsigned long long)OH * OW * (a.cout >> 3), (unsigned)(a.cout >> 3));
-        a.fd_oc8 = fastdiv((unsigned)(a.cout >> 3));
-    }
-    const int zsplit = dn_cdiv(chunks, cpw);
-    DN_REQUIRE((long)tiles_y * zsplit <= 65535 && a.n <= 65535, "expand+depthwise: grid too large");
-    if (proj) DN_REQUIRE((DROWS / 32) * dn_cdiv(a.cout, 32) <= NT / 64, "expand+depthwise+project: %d output units for %d waves", (DROWS / 32) * dn_cdiv(a.cout, 32), NT / 64);
-    // the A fragments of the expand live in registers: 2 full K steps + the tail/bias step cover cin <= 40 (fewer registers -> more
-    // waves), else 8. The block shapes of the backbones (cin 16 / 24 + project) get compile-time X row widths.
-    if (!exp) return proj ? launch_k<K, S, OH, OW, 2, false, true, 0>(a, tiles_x, tiles_y, zsplit, lds, s) : DN_E_UNSUPPORTED;
-    if (proj) {
-        if (a.xw == 24) return launch_k<K, S, OH, OW, 2, true, true, 3>(a, tiles_x, tiles_y, zsplit, lds, s);
-        if (a.xw == 40 && a.cin <= 40) return launch_k<K, S, OH, OW, 2, true, true, 5>(a, tiles_x, tiles_y, zsplit, lds, s);
-        if (a.xw == 56) return launch_k<K, S, OH, OW, 2, true, true, 7>(a, tiles_x, tiles_y, zsplit, lds, s);        // cin 40
-        if (a.cin <= 40) return launch_k<K, S, OH, OW, 2, true, true, 0>(a, tiles_x, tiles_y, zsplit, lds, s);
-        if (a.xw == 88) return launch_k<K, S, OH, OW, 5, true, true, 11>(a, tiles_x, tiles_y, zsplit, lds, s);       // cin 80: the 20 x 20 blocks
-        if (a.cin <= 88) return launch_k<K, S, OH, OW, 5, true, true, 0>(a, tiles_x, tiles_y, zsplit, lds, s);
-        if (a.xw == 104) return launch_k<K, S, OH, OW, 6, true, true, 13>(a, tiles_x, tiles_y, zsplit, lds, s);      // cin 96
-        return launch_k<K, S, OH, OW, XKS, true, true, 0>(a, tiles_x, tiles_y, zsplit, lds, s);
-    }
-    if (a.xw == 56) return launch_k<K, S, OH, OW, 2, true, false, 7>(a, tiles_x, tiles_y, zsplit, lds, s);          // cin 40
-    if (a.xw == 40 && a.cin <= 40) return launch_k<K, S, OH, OW, 2, true, false, 5>(a, tiles_x, tiles_y, zsplit, lds, s);   // cin 24 / 32
-    if (a.cin <= 40) return launch_k<K, S, OH, OW, 2, true, false, 0>(a, tiles_x, tiles_y, zsplit, lds, s);
-    if (a.xw == 88) return launch_k<K, S, OH, OW, 5, true, false, 11>(a, tiles_x, tiles_y, zsplit, lds, s);         // cin 80 (squeeze-excitation blocks of the 20 x 20 / 10 x 10 maps)
-    return launch_k<K, S, OH, OW, XKS, true, false, 0>(a, tiles_x, tiles_y, zsplit, lds, s);
+int launch_rung(const ExpDwArgs& a, const ExpDwChoice& c, hipStream_t s) {
+    auto is = [&](int ksm, bool exp, bool proj, int xw8) { return c.ksm == ksm && c.exp == exp && c.proj == proj && c.xw8 == xw8; };
+    if (is(2, false, true, 0)) return launch_form<K, S, OH, OW, 2, false, true, 0>(a, c, s);
+    if (is(2, true, true, 3)) return launch_form<K, S, OH, OW, 2, true, true, 3>(a, c, s);
+    if (is(2, true, true, 5)) return launch_form<K, S, OH, OW, 2, true, true, 5>(a, c, s);
+    if (is(2, true, true, 7)) return launch_form<K, S, OH, OW, 2, true, true, 7>(a, c, s);
+    if (is(5, true, true, 11)) return launch_form<K, S, OH, OW, 5, true, true, 11>(a, c, s);
+    if (is(5, true, true, 0)) return launch_form<K, S, OH, OW, 5, true, true, 0>(a, c, s);
+    if (is(6, true, true, 13)) return launch_form<K, S, OH, OW, 6, true, true, 13>(a, c, s);
+    if (is(XKS, true, true, 0)) return launch_form<K, S, OH, OW, XKS, true, true, 0>(a, c, s);
+    if (is(2, true, false, 7)) return launch_form<K, S, OH, OW, 2, true, false, 7>(a, c, s);
+    if (is(2, true, false, 5)) return launch_form<K, S, OH, OW, 2, true, false, 5>(a, c, s);
+    if (is(2, true, false, 0)) return launch_form<K, S, OH, OW, 2, true, false, 0>(a, c, s);
+    if (is(5, true, false, 11)) return launch_form<K, S, OH, OW, 5, true, false, 11>(a, c, s);
+    if (is(XKS, true, false, 0)) return launch_form<K, S, OH, OW, XKS, true, false, 0>(a, c, s);
+    return no_instantiation(c);
 }
 
+// the tiles expdw_tile answers: 5 x 5, 5 x 10, and by stride 10 x 10 and 8 x 16 (1) or 8 x 8 (2)
 template <int K, int S>
-int launch_ks(const ExpDwArgs& a, int oh, int ow, hipStream_t s) {
-    if (oh == 4) return launch_t<K, S, 4, 8>(a, s);
-    if (oh == 8 && ow == 8) return launch_t<K, S, 8, 8>(a, s);
-    if (oh == 8) {
-        if constexpr (S == 1) return launch_t<K, S, 8, 16>(a, s);
-        else return launch_t<K, S, 8, 8>(a, s);
+int launch_tile(const ExpDwArgs& a, const ExpDwChoice& c, hipStream_t s) {
+    if (c.oh == 5 && c.ow == 5) return launch_rung<K, S, 5, 5>(a, c, s);
+    if (c.oh == 5 && c.ow == 10) return launch_rung<K, S, 5, 10>(a, c, s);
+    if constexpr (S == 1) {
+        if (c.oh == 10 && c.ow == 10) return launch_rung<K, S, 10, 10>(a, c, s);
+        if (c.oh == 8 && c.ow == 16) return launch_rung<K, S, 8, 16>(a, c, s);
+    } else {
+        if (c.oh == 8 && c.ow == 8) return launch_rung<K, S, 8, 8>(a, c, s);
     }
-    if constexpr (S == 1) { if (oh == 10) return launch_t<K, S, 10, 10>(a, s); }
-    if (ow == 10) return launch_t<K, S, 5, 10>(a, s);
-    return launch_t<K, S, 5, 5>(a, s);
+    return no_instantiation(c);
 }
 
 }  // namespace
-
-void expdw_tile(int Ho, int Wo, int stride, int* oh, int* ow, int proj_cout = 0) {
-    if (Wo <= 5 && Ho <= 5) { *oh = 5; *ow = 5; }
-    else if (Wo <= 10) { *oh = 5; *ow = 10; }
-    else if (Wo < 32 && Wo % 16 != 0) {                     // 19x19 / 20x20 maps: 10-wide tiles waste nothing
-        if (stride == 1) { *oh = 10; *ow = 10; } else { *oh = 5; *ow = 10; }       // (measured again in round 4 on the V2 model at 300 x 300: 5 x 10 tiles there are 2.4 % slower, although the 10 x 10 variants with cin >= 64 spill 36 - 44 B per lane)
-        // with a project stage the (pixel tile x channel tile) units must fit the 8 waves: 100 pixels x 80 channels = 12 units, 50 x 80 = 6
-        if (proj_cout > 0 && ((*oh * *ow + 31) / 32) * ((proj_cout + 31) / 32) > NT / 64) { *oh = 5; *ow = 10; }
-    }
-    else { *oh = 8; *ow = (stride == 1) ? 16 : 8; }
-}
-
-int expdw_tiles_per_image(int Ho, int Wo, int stride) {
-    int oh, ow;
-    expdw_tile(Ho, Wo, stride, &oh, &ow);
-    return dn_cdiv(Ho, oh) * dn_cdiv(Wo, ow);
-}
-
-bool expdw_supported(int cin, int cexp, int k, int stride) {
-    return cin % 8 == 0 && cin <= 16 * XKS && cexp % 8 == 0 && (k == 3 || k == 5) && (stride == 1 || stride == 2);
-}
-
-// the project stage keeps one MFMA accumulator per wave: (pixels of the tile / 32) x (cout / 32) units must fit the 8 waves
-bool expdw_project_supported(int cexp, int cout, int Ho, int Wo, int stride) {
-    int oh, ow;
-    expdw_tile(Ho, Wo, stride, &oh, &ow, cout);
-    return cexp % 8 == 0 && cout % 8 == 0 && ((oh * ow + 31) / 32) * ((cout + 31) / 32) <= NT / 64;
-}
 
 int launch_expdw(const ExpDwArgs& a0, hipStream_t s) {
     ExpDwArgs a = a0;
@@ -852,30 +787,21 @@ int launch_expdw(const ExpDwArgs& a0, hipStream_t s) {
     DN_REQUIRE(!a.w3 || (!a.pool && expdw_project_supported(a.cexp, a.cout, a.Ho, a.Wo, a.stride)), "expand+depthwise+project: unsupported cout=%d / tile", a.cout);
     DN_REQUIRE(!a.has_res || (a.w3 && a.stride == 1 && a.cout == a.cin), "expand+depthwise+project: residual needs stride 1 and cout == cin");
     DN_REQUIRE(a.n > 0 && a.H > 0 && a.W > 0 && a.Ho > 0 && a.Wo > 0, "expand+depthwise: empty problem");
-    a.xw = ((a.cin + 15) / 16) * 16 + 8;
-    int oh, ow;
-    expdw_tile(a.Ho, a.Wo, a.stride, &oh, &ow, a.w3 ? a.cout : 0);
-    // the per-tap body (expdw_direct.hip) for the one-chunk stride-2 block 16 -> 64 -> cout. The launch keeps the label of the body it replaces
-    // (expdw_one_kernel on the 8 x 8 tiles of the large maps, launch_kw): plan signatures and bench.py's families do not see the choice.
-    if (!g_xd_stamps && dn_knob("DN_EXPDW_DIRECT", 1)) {
-        const int bh = expdw_direct_band(a);
-        if (bh > 0) {
-            if (oh == 8 && ow == 8 && dn_knob("DN_EXPDW_PERSIST", 1)) dn_note_kernel("expdw_one_kernel<3,2,8,8,2>");
-            else dn_note_kernel("expdw_kernel<3,2,%d,%d,2,true,true>", oh, ow);
-            return launch_expdw_direct(a, bh, s);
-        }
+    const ExpDwChoice c = expdw_choose(a, g_xd_stamps != nullptr);
+    DN_REQUIRE(c.body != ExpDwChoice::NONE || c.lds <= EXPDW_LDS_MAX, "expand+depthwise: LDS %zu B exceeds 160 KB", c.lds);
+    DN_REQUIRE(c.body != ExpDwChoice::NONE, "expand+depthwise: grid too large");
+    // the launcher-owned fields, from the answer
+    a.xw = c.xw; a.chunks_per_wg = c.cpw; a.stage_out = c.stage_out;
+    if (c.proj) a.fd_oc8 = fastdiv((unsigned)(a.cout >> 3));
+    {   // dev: DN_EXPDW_STAMP_SEL = 10 * H + stride stamps only the launches of that shape (every launch writes the same buffer)
+        const int sel = g_xd_stamps ? dn_knob("DN_EXPDW_STAMP_SEL", 0) : 0;
+        a.stamps = (sel == 0 || sel == 10 * a.H + a.stride) ? g_xd_stamps : nullptr;
     }
-    // the row-reuse body (expdw_rows.hip) for the one-chunk stride-1 block 24 -> 72 -> cout, under the label of the body it replaces in the same way
-    if (!g_xd_stamps && dn_knob("DN_EXPDW_ROWS", 1)) {
-        const int bh = expdw_rows_band(a);
-        if (bh > 0) {
-            if (oh == 8 && ow == 16 && dn_knob("DN_EXPDW_PERSIST", 1)) dn_note_kernel("expdw_one_kernel<3,1,8,16,2>");
-            else dn_note_kernel("expdw_kernel<3,1,%d,%d,2,true,true>", oh, ow);
-            return launch_expdw_rows(a, bh, s);
-        }
-    }
-    if (a.k == 3 && a.stride == 1) return launch_ks<3, 1>(a, oh, ow, s);
-    if (a.k == 3 && a.stride == 2) return launch_ks<3, 2>(a, oh, ow, s);
-    if (a.k == 5 && a.stride == 1) return launch_ks<5, 1>(a, oh, ow, s);
-    return launch_ks<5, 2>(a, oh, ow, s);
+    dn_note_kernel("%s", c.label);
+    if (c.body == ExpDwChoice::DIRECT) return launch_expdw_direct(a, c.band, s);
+    if (c.body == ExpDwChoice::ROWS) return launch_expdw_rows(a, c.band, s);
+    if (a.k == 3 && a.stride == 1) return launch_tile<3, 1>(a, c, s);
+    if (a.k == 3 && a.stride == 2) return launch_tile<3, 2>(a, c, s);
+    if (a.k == 5 && a.stride == 1) return launch_tile<5, 1>(a, c, s);
+    return launch_tile<5, 2>(a, c, s);
 }

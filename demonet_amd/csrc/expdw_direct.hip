@@ -1,6 +1,6 @@
 // Fused expand + depthwise 3x3 stride 2 + project for the one-chunk block 16 -> 64 -> cout (the 160 x 160 -> 80 x 80 block of MobileNetV3):
 // the expanded value of EACH TAP comes out of the matrix cores in the accumulator position of the output pixel that needs it and goes straight
-// into the depthwise sum. A second body for the launch that expdw.hip serves (launch_expdw selects it: DN_EXPDW_DIRECT, default 1); same
+// into the depthwise sum. A second body for the launch that expdw.hip serves (expdw_choose selects it, choice.h: DN_EXPDW_DIRECT, default 1); same
 // reference ops (mobilenetv3.py:72-95, BN folded).
 //
 // Why: at stride 2 an expanded value is used by 2.25 output pixels on average, and the expand is ONE 16-deep matrix step plus the bias step.

@@ -1,6 +1,6 @@
 // Fused expand + depthwise 3x3 stride 1 + project (+ residual) for the one-chunk block 24 -> 72 -> cout (the 80 x 80 block of MobileNetV3): a wave
 // walks DOWN a 32-pixel column strip, expands every input row ONCE on the matrix cores and keeps the last three expanded rows in registers, already in
-// the accumulator layout. A third body for the launch that expdw.hip serves (launch_expdw selects it: DN_EXPDW_ROWS, default 1); same reference ops
+// the accumulator layout. A third body for the launch that expdw.hip serves (expdw_choose selects it, choice.h: DN_EXPDW_ROWS, default 1); same reference ops
 // (mobilenetv3.py:72-95, BN folded).
 //
 // Why: at stride 1 every expanded value has nine uses, so the per-tap recompute of expdw_direct.hip does not carry over, and expdw_one_kernel pays for

@@ -1795,7 +1795,7 @@ void depthwise_debug_limits(const DwArgs& a, int tw, bool* in_range, size_t* wld
 //   "headfuse"  n H W C nc0 nc1 stride0 stride1                                 -> head_fused_level_supported (supported=)
 //   "headpost"  n H W aloc K A                                                  -> head_fused_post_supported of one level with the epilogue (supported=)
 //   "patch_blocks" n h w                                                        -> conv_patch_resident_blocks (blocks=, launched=: below the launcher's 2^30)
-//   "expdw"     n h w cin cexp cout k stride act1 act2 has_res pool             -> expdw_direct_band / expdw_rows_band (body=direct / rows / tiled, band=)
+//   "expdw"     n h w cin cexp cout k stride act1 act2 has_res pool             -> expdw_choose (body=direct / rows / tiled / none, band=, label=, tile=<oh>x<ow>); cout 0: no project stage, act1 -1: no expand stage
 extern "C" __attribute__((visibility("default"))) int dn_debug_choice(const char* family, const int64_t* d, int nd, char* buf, int capacity) {
     DN_REQUIRE(family && d && buf && capacity > 0, "dn_debug_choice: null argument");
     static const half_t dummy_h[8] = {};
@@ -1895,13 +1895,16 @@ extern "C" __attribute__((visibility("default"))) int dn_debug_choice(const char
     if (f == "expdw") {
         DN_REQUIRE(nd == 12 && d[0] > 0 && d[1] > 0 && d[2] > 0 && d[6] >= 1 && d[7] >= 1, "dn_debug_choice: expdw takes n h w cin cexp cout k stride act1 act2 has_res pool");
         ExpDwArgs a{};
-        a.x = a.w1 = a.wd = a.w3 = dummy_h; a.b1 = a.bd = a.b3 = dummy_f; a.pool = d[11] ? dummy_out : nullptr;
-        a.n = (int)d[0]; a.H = (int)d[1]; a.W = (int)d[2]; a.cin = (int)d[3]; a.cexp = (int)d[4]; a.cout = (int)d[5]; a.k = (int)d[6]; a.stride = (int)d[7];
+        a.x = a.wd = dummy_h; a.bd = dummy_f; a.pool = d[11] ? dummy_out : nullptr;
+        if (d[8] >= 0) { a.w1 = dummy_h; a.b1 = dummy_f; }
+        if (d[5] > 0) { a.w3 = dummy_h; a.b3 = dummy_f; }
+        a.n = (int)d[0]; a.H = (int)d[1]; a.W = (int)d[2]; a.cin = (int)d[3]; a.cexp = (int)d[4]; a.cout = a.w3 ? (int)d[5] : a.cexp; a.k = (int)d[6]; a.stride = (int)d[7];
         a.pad = (a.k - 1) / 2; a.Ho = (a.H + 2 * a.pad - a.k) / a.stride + 1; a.Wo = (a.W + 2 * a.pad - a.k) / a.stride + 1;
-        a.act1 = (int)d[8]; a.act2 = (int)d[9]; a.has_res = (int)d[10]; a.xq = xcd_images_per_group(a.n);
-        const int bh = dn_knob("DN_EXPDW_DIRECT", 1) ? expdw_direct_band(a) : 0;
-        const int rb = bh == 0 && dn_knob("DN_EXPDW_ROWS", 1) ? expdw_rows_band(a) : 0;
-        snprintf(buf, (size_t)capacity, "body=%s band=%d", bh > 0 ? "direct" : (rb > 0 ? "rows" : "tiled"), bh > 0 ? bh : rb);
+        a.act1 = a.w1 ? (int)d[8] : 0; a.act2 = (int)d[9]; a.has_res = (int)d[10]; a.xq = xcd_images_per_group(a.n);
+        DN_REQUIRE(a.Ho > 0 && a.Wo > 0, "dn_debug_choice: expdw with an empty output");
+        const ExpDwChoice c = expdw_choose(a, false);
+        static const char* const bodies[] = {"none", "direct", "rows", "tiled", "tiled"};       // NONE, DIRECT, ROWS, ONE_PERSIST, TILED
+        snprintf(buf, (size_t)capacity, "body=%s band=%d label=%s tile=%dx%d", bodies[c.body], c.band, c.label, c.oh, c.ow);
         return DN_OK;
     }
     dn_set_error("dn_debug_choice: unknown family '%s'", family);

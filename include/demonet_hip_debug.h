@@ -51,9 +51,11 @@ DN_API int dn_debug_stem(const float* img_dev, const float* w_dev, const float* 
  *   "headfuse"  n H W C nc0 nc1 out_img_stride0 out_img_stride1     (supported=: the level may join the fused head launch)
  *   "headpost"  n H W anchors_per_location K A                      (supported=: the level's workgroups may run the softmax / decode epilogue)
  *   "patch_blocks" n h w        (blocks=: 16 x 16 blocks of a conv_patch_resident_kernel launch; launched=: below the launcher's limit)
- *   "expdw"     n h w cin cexp cout k stride act1 act2 has_res pool     (body=direct: the per-tap body of expdw_direct.hip takes the launch,
- *               band= its output rows per workgroup; body=rows: the row-reuse body of expdw_rows.hip, band= its output rows per wave; body=tiled:
- *               the bodies of expdw.hip; reads DN_EXPDW_DIRECT / DN_EXPDW_DIRECT_BAND / DN_EXPDW_ROWS / DN_EXPDW_ROWS_BAND)
+ *   "expdw"     n h w cin cexp cout k stride act1 act2 has_res pool     (expdw_choose's answer, the function launch_expdw asks. cout 0: no project
+ *               stage; act1 -1: no expand stage. body=direct: the per-tap body of expdw_direct.hip takes the launch, band= its output rows per
+ *               workgroup; body=rows: the row-reuse body of expdw_rows.hip, band= its output rows per wave; body=tiled: the bodies of expdw.hip;
+ *               body=none: no body takes it; label= what the launch notes, whichever body runs; tile= the output tile <oh>x<ow> of the tiled
+ *               bodies; reads DN_EXPDW_DIRECT / DN_EXPDW_DIRECT_BAND / DN_EXPDW_ROWS / DN_EXPDW_ROWS_BAND / DN_EXPDW_PERSIST / DN_EXPDW_ONE)
  * 0 on success. */
 DN_API int dn_debug_choice(const char* family, const int64_t* dims, int ndims, char* buf, int capacity);
 

@@ -44,13 +44,14 @@ def _run(monkeypatch, n, h, w, cin, cexp, cout, k=3, s=2, act1=RELU, act2=RELU, 
                      ("per_tile", {"DN_EXPDW_DIRECT": "0", "DN_EXPDW_PERSIST": "0"})):
         for kk, v in env.items():
             monkeypatch.setenv(kk, v)
-        body = _choice(L, n, h, w, cin, cexp, cout, k, s, act1, act2, res)["body"]
-        assert body == ("direct" if key == "direct" and direct else "tiled"), (key, body)
+        choice = _choice(L, n, h, w, cin, cexp, cout, k, s, act1, act2, res)
+        assert choice["body"] == ("direct" if key == "direct" and direct else "tiled"), (key, choice)
         out = torch.full((n, ho, wo, cout), float("nan"), dtype=torch.half, device="cuda")
         for _ in range(2):
             L.check(lib.dn_expand_depthwise(_ptr(x), _ptr(w1), _ptr(b1), _ptr(wd), _ptr(bd), _ptr(w3), _ptr(b3), _ptr(out), None,
                                             n, h, w, cin, cexp, cout, k, s, act1, act2, int(res),
                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "dn_expand_depthwise")
+            assert L.debug_last_kernel() == choice["label"]
         torch.cuda.synchronize()
         outs[key] = out
     assert torch.isfinite(outs["direct"].float()).all()
@@ -113,7 +114,8 @@ def test_model_heads_bit_identical(monkeypatch):
     body's bit for bit, also with NaN patterns left in every LDS byte and vector register in front of every launch (DN_POISON=1, plain launches)."""
     L, _ = _lib()
     monkeypatch.setenv("DN_EXPDW_DIRECT", "1")
-    assert _choice(L, 2, 160, 160, 16, 64, 24, 3, 2, RELU, RELU, False) == {"body": "direct", "band": 4}
+    choice = _choice(L, 2, 160, 160, 16, 64, 24, 3, 2, RELU, RELU, False)
+    assert (choice["body"], choice["band"]) == ("direct", 4)
     base = _heads(monkeypatch, {"DN_EXPDW_DIRECT": "0"})
     new = _heads(monkeypatch, {"DN_EXPDW_DIRECT": "1"})
     poisoned = _heads(monkeypatch, {"DN_EXPDW_DIRECT": "1", "DN_POISON": "1", "DN_GRAPH": "0"})

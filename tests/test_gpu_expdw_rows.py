@@ -44,13 +44,14 @@ def _run(monkeypatch, n, h, w, cin=24, cexp=72, cout=24, k=3, s=1, act1=RELU, ac
                      ("per_tile", {"DN_EXPDW_ROWS": "0", "DN_EXPDW_PERSIST": "0"})):
         for kk, v in env.items():
             monkeypatch.setenv(kk, v)
-        body = _choice(L, n, h, w, cin, cexp, cout, k, s, act1, act2, res)["body"]
-        assert body == ("rows" if key == "rows" and rows else "tiled"), (key, body)
+        choice = _choice(L, n, h, w, cin, cexp, cout, k, s, act1, act2, res)
+        assert choice["body"] == ("rows" if key == "rows" and rows else "tiled"), (key, choice)
         out = torch.full((n, ho, wo, cout), float("nan"), dtype=torch.half, device="cuda")
         for _ in range(2):
             L.check(lib.dn_expand_depthwise(_ptr(x), _ptr(w1), _ptr(b1), _ptr(wd), _ptr(bd), _ptr(w3), _ptr(b3), _ptr(out), None,
                                             n, h, w, cin, cexp, cout, k, s, act1, act2, int(res),
                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "dn_expand_depthwise")
+            assert L.debug_last_kernel() == choice["label"]
         torch.cuda.synchronize()
         outs[key] = out
     assert torch.isfinite(outs["rows"].float()).all()
@@ -96,7 +97,8 @@ def test_other_band_heights(band, monkeypatch):
     monkeypatch.setenv("DN_EXPDW_ROWS_BAND", str(band))
     L, _ = _lib()
     monkeypatch.setenv("DN_EXPDW_ROWS", "1")
-    assert _choice(L, 2, 11, 61, 24, 72, 24, 3, 1, RELU, RELU, True) == {"body": "rows", "band": band}
+    choice = _choice(L, 2, 11, 61, 24, 72, 24, 3, 1, RELU, RELU, True)
+    assert (choice["body"], choice["band"]) == ("rows", band)
     _run(monkeypatch, 2, 11, 61)
 
 

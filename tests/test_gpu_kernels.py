@@ -346,6 +346,8 @@ def test_expand_depthwise(n, h, w, cin, cexp, cout, k, s, expand, project, pool,
                                  n, h, w, cin, cexp, cout, k, s, act1, act2, int(res),
                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
     L.check(rc, "dn_expand_depthwise")
+    # the launcher took what the choice function answers for the shape (cout 0: no project stage, act1 -1: no expand stage)
+    assert L.debug_last_kernel() == L.debug_choice("expdw", n, h, w, cin, cexp, cout if project else 0, k, s, act1 if expand else -1, act2, int(res), int(pool))["label"]
     torch.cuda.synchronize()
     got = out.cpu().float().permute(0, 3, 1, 2)
     tol = dict(rtol=1e-2, atol=2e-2) if project else dict(rtol=4e-3, atol=4e-3)
@@ -355,7 +357,8 @@ def test_expand_depthwise(n, h, w, cin, cexp, cout, k, s, expand, project, pool,
 
 
 @pytest.mark.parametrize("n,h,w,cin,cexp,cout,k,s,res,act", [
-    (12, 36, 44, 16, 64, 24, 3, 2, False, 1),       # b2-like, XCD-grouped (12 images: ragged last group), ragged tile edges
+    (12, 68, 76, 16, 64, 24, 3, 2, False, 1),       # b2-like, XCD-grouped (12 images: ragged last group), ragged tile edges (34 x 38 outputs in 8 x 8 tiles;
+                                                    # the 36 x 44 map that stood here has 5 x 10 tiles, which the persistent form never takes)
     (3, 160, 160, 16, 64, 24, 3, 2, False, 1),      # the 160 x 160 block itself, plain mapping: 300 tiles on 300 workgroups ... and
     (40, 160, 160, 16, 64, 24, 3, 2, False, 1),     # ... 4 000 tiles on 512: every workgroup walks 7 - 8 tiles
     (19, 80, 80, 24, 72, 24, 3, 1, True, 1),        # b3-like: 72 channels taken whole, residual from the staged region, 50 tiles per image
@@ -365,8 +368,11 @@ def test_expand_depthwise(n, h, w, cin, cexp, cout, k, s, expand, project, pool,
 def test_expdw_persistent_bit_identical(n, h, w, cin, cexp, cout, k, s, res, act, monkeypatch):
     """expdw_one_kernel (round 4, default for the single-chunk full blocks): 512 resident workgroups walk the tiles, the next tile's input
     region copied by LDS-DMA under the current tile's depthwise / project stages, the finished tile stored during the next one. Same
-    arithmetic at the same rounding points as one workgroup per tile (expdw_kernel, DN_EXPDW_PERSIST=0): outputs equal bit for bit."""
+    arithmetic at the same rounding points as one workgroup per tile (expdw_kernel, DN_EXPDW_PERSIST=0): outputs equal bit for bit. The two other
+    bodies of these shapes (DN_EXPDW_DIRECT, DN_EXPDW_ROWS) are switched off: the launch's label names the body that ran."""
     L, lib = _lib()
+    monkeypatch.setenv("DN_EXPDW_DIRECT", "0")
+    monkeypatch.setenv("DN_EXPDW_ROWS", "0")
     g = torch.Generator().manual_seed(h * 3 + cexp + n)
     x = torch.randn(n, h, w, cin, generator=g).half().cuda()
     w1 = (torch.randn(cexp, cin, generator=g) / cin ** 0.5).half().cuda()
@@ -385,6 +391,7 @@ def test_expdw_persistent_bit_identical(n, h, w, cin, cexp, cout, k, s, res, act
             L.check(lib.dn_expand_depthwise(_ptr(x), _ptr(w1), _ptr(b1), _ptr(wd), _ptr(bd), _ptr(w3), _ptr(b3), _ptr(out), None,
                                             n, h, w, cin, cexp, cout, k, s, act, act, int(res),
                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "dn_expand_depthwise")
+            assert L.debug_last_kernel().startswith("expdw_one_kernel<" if flag == "1" else "expdw_kernel<")
         torch.cuda.synchronize()
         outs.append(out)
     assert torch.isfinite(outs[1].float()).all()
