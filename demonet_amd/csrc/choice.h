@@ -431,9 +431,11 @@ struct ExpDwChoice {
     int k = 0, stride = 0, oh = 0, ow = 0;              // kernel size, stride, output tile
     int ksm = 0, xw8 = 0;                               // full K steps of the expand held in registers; X row width in 16-byte pieces where it is a compile-time constant (0: runtime)
     bool exp = false, proj = false, wide = false, one = false;   // expand / project stage; a last chunk of 72 channels taken whole; the chunk loop is one chunk
+    bool whole = false;                                 // TILED: the phases walked once over the whole expanded width (expdw_whole_kernel, expdw_whole.hip), not per 64-channel chunk
     int band = 0;                                       // DIRECT, ROWS: output rows per band
     int cpw = 0, zsplit = 1, xw = 0, stage_out = 0;     // chunks per workgroup and their split over grid.y; halfs per X row; the projected tile leaves through LDS
     size_t lds = 0, lds_p = 0;                          // LDS bytes of expdw_kernel / of expdw_one_kernel (+ the tile's own output buffer)
+    size_t lds_w = 0;                                   // LDS bytes of expdw_whole_kernel (0: the shape is not its)
     char label[64] = "";                                // the launch's label: ALWAYS the tiled choice's, whichever body runs (plan signatures and bench families do not see DIRECT / ROWS)
 };
 
@@ -470,6 +472,32 @@ constexpr int expdw_region_rows(int k, int stride, int oh, int ow) { return (((o
 inline bool expdw_persist_supported(const ExpDwArgs& a, const ExpDwChoice& c, bool stamped) {
     return c.exp && c.proj && c.ksm <= 2 && (c.xw8 == 3 || c.xw8 == 5) && c.k == 3 && c.oh == 8 && c.ow == (c.stride == 1 ? 16 : 8) && !a.pool && !stamped &&
            a.cout % 8 == 0 && a.cout <= 256 && c.lds_p <= EXPDW_PERSIST_LDS_MAX && fd_ok((unsigned long long)c.oh * c.ow * (a.cout >> 3), (unsigned)(a.cout >> 3));
+}
+
+// The whole-width form of the tiled body (expdw_whole_kernel, expdw_whole.hip) is built for the multi-chunk full blocks of the 20 x 20 maps: 3x3 stride 1 on the
+// 5 x 10 tile, cin 80 (88-half X rows, five full K steps), any expanded width whose whole E tile fits beside the rest at two workgroups per CU. Its LDS: the
+// depthwise output D[64][round16(cexp) + 8] laid over the dead X region [96][88] + 8, E[96][cexp, + 8 where that makes the 16-byte pieces of a row an odd number] (the finished tile is staged over it),
+// all nine depthwise weight rows, the depthwise bias, the project bias.
+constexpr int EXPDW_WHOLE_CIN = 80, EXPDW_WHOLE_OH = 5, EXPDW_WHOLE_OW = 10, EXPDW_WHOLE_ROWS = 96, EXPDW_WHOLE_DROWS = 64;
+constexpr int EXPDW_WHOLE_CEXP_MAX = 224;       // seven 32-channel tiles of the expand on the eight waves, fourteen K steps of the projection in registers
+constexpr int expdw_whole_front_halfs(int cexp) {
+    const int x = EXPDW_WHOLE_ROWS * (EXPDW_WHOLE_CIN + 8) + 8, d = EXPDW_WHOLE_DROWS * (((cexp + 15) & ~15) + 8);
+    return x > d ? x : d;
+}
+// halfs per E row: an odd number of 16-byte pieces. The expand writes 8-byte pieces down 32 rows: an even count puts them on 4 (cexp 224) or 2 (cexp 128) of the 32
+// banks -- measured alone, 128 channels without the pad: 12.3 us against the chunk loop's 10.9
+constexpr int expdw_whole_erow(int cexp) { return ((cexp >> 3) & 1) ? cexp : cexp + 8; }
+constexpr size_t expdw_whole_lds(int cexp) {
+    return ((size_t)expdw_whole_front_halfs(cexp) + (size_t)EXPDW_WHOLE_ROWS * expdw_whole_erow(cexp) + 9 * (size_t)cexp) * sizeof(half_t) + ((size_t)cexp + 256) * sizeof(float);
+}
+static_assert(expdw_whole_lds(EXPDW_WHOLE_CEXP_MAX) <= EXPDW_PERSIST_LDS_MAX && expdw_whole_lds(EXPDW_WHOLE_CEXP_MAX + 8) > EXPDW_PERSIST_LDS_MAX, "the widest block that keeps two workgroups per CU");
+// no pooled sums, no stamps; the staged tile must fit the dead E rows and the (row tile, channel tile) units of the projection the 8 waves; the nine
+// weight rows are staged by one 16-byte piece per thread
+inline bool expdw_whole_supported(const ExpDwArgs& a, const ExpDwChoice& c, bool stamped) {
+    return c.exp && c.proj && c.k == 3 && c.stride == 1 && a.pad == 1 && c.oh == EXPDW_WHOLE_OH && c.ow == EXPDW_WHOLE_OW && a.cin == EXPDW_WHOLE_CIN && !a.pool && !stamped &&
+           a.cexp % 8 == 0 && a.cexp >= 8 && a.cexp <= EXPDW_WHOLE_CEXP_MAX && expdw_whole_lds(a.cexp) <= EXPDW_PERSIST_LDS_MAX && 9 * (a.cexp >> 3) <= EXPDW_NT &&
+           a.cout % 8 == 0 && a.cout >= 8 && a.cout <= 256 && (EXPDW_WHOLE_DROWS / 32) * dn_cdiv(a.cout, 32) <= EXPDW_NT / 64 && c.stage_out &&
+           (size_t)c.oh * c.ow * a.cout <= (size_t)EXPDW_WHOLE_ROWS * a.cexp && c.zsplit == 1;
 }
 
 // `a` as launch_expdw has validated it (its DN_REQUIREs; the launcher-filled fields are not read). stamped: a dev build with phase stamps armed
@@ -529,6 +557,14 @@ inline ExpDwChoice expdw_choose(const ExpDwArgs& a, bool stamped) {
     }
     if (!stamped && dn_knob("DN_EXPDW_ROWS", 1)) {
         if (const int bh = expdw_rows_band(a)) { c.body = ExpDwChoice::ROWS; c.band = bh; return c; }
+    }
+    // The whole-width form of the tiled body: a flag like `one` and `wide` -- body, label, band and tile stay. DN_EXPDW_WHOLE: 1 = the shapes measured faster
+    // on MI355X, which are the two multi-chunk widths of the 20 x 20 blocks of MobileNetV3, 200 (four passes of the chunk loop, the last for 8 channels) and 184
+    // (three); every other width the form can run keeps the chunk loop until someone measures it. 0 = never, 2 = wherever it can run (tests, A/B).
+    if (c.body == ExpDwChoice::TILED && !c.one && expdw_whole_supported(a, c, stamped)) {
+        c.lds_w = expdw_whole_lds(a.cexp);
+        const int knob = dn_knob("DN_EXPDW_WHOLE", 1);
+        c.whole = knob >= 2 || (knob == 1 && (a.cexp == 200 || a.cexp == 184));
     }
     return c;
 }

@@ -358,6 +358,9 @@ int launch_expdw_direct(const ExpDwArgs& a, int bh, hipStream_t s);
 // expdw_rows_band: its capability test -- output rows per band, 0 = not its shape; launch_expdw_rows enqueues it.
 int expdw_rows_band(const ExpDwArgs& a);
 int launch_expdw_rows(const ExpDwArgs& a, int bh, hipStream_t s);
+// expdw_whole.hip: the tiled body with its phases walked once over the whole expanded width (the multi-chunk blocks of the 20 x 20 maps). Its capability test
+// and LDS arithmetic are expdw_whole_supported / expdw_whole_lds (choice.h); launch_expdw_whole enqueues it with that many LDS bytes.
+int launch_expdw_whole(const ExpDwArgs& a, size_t lds, hipStream_t s);
 
 
 // Pyramid levels of the anchor axis. The class-major score array of the post-process is stored ANCHOR-MAJOR WITHIN A LEVEL:

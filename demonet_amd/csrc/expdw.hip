@@ -800,6 +800,7 @@ int launch_expdw(const ExpDwArgs& a0, hipStream_t s) {
     dn_note_kernel("%s", c.label);
     if (c.body == ExpDwChoice::DIRECT) return launch_expdw_direct(a, c.band, s);
     if (c.body == ExpDwChoice::ROWS) return launch_expdw_rows(a, c.band, s);
+    if (c.body == ExpDwChoice::TILED && c.whole) return launch_expdw_whole(a, c.lds_w, s);
     if (a.k == 3 && a.stride == 1) return launch_tile<3, 1>(a, c, s);
     if (a.k == 3 && a.stride == 2) return launch_tile<3, 2>(a, c, s);
     if (a.k == 5 && a.stride == 1) return launch_tile<5, 1>(a, c, s);

@@ -1796,6 +1796,7 @@ void depthwise_debug_limits(const DwArgs& a, int tw, bool* in_range, size_t* wld
 //   "headpost"  n H W aloc K A                                                  -> head_fused_post_supported of one level with the epilogue (supported=)
 //   "patch_blocks" n h w                                                        -> conv_patch_resident_blocks (blocks=, launched=: below the launcher's 2^30)
 //   "expdw"     n h w cin cexp cout k stride act1 act2 has_res pool             -> expdw_choose (body=direct / rows / tiled / none, band=, label=, tile=<oh>x<ow>); cout 0: no project stage, act1 -1: no expand stage
+//   "expdw_whole" the same twelve numbers                                       -> expdw_choose's flag of the tiled body (whole=, lds= the whole-width form's LDS bytes, 0 without it)
 extern "C" __attribute__((visibility("default"))) int dn_debug_choice(const char* family, const int64_t* d, int nd, char* buf, int capacity) {
     DN_REQUIRE(family && d && buf && capacity > 0, "dn_debug_choice: null argument");
     static const half_t dummy_h[8] = {};
@@ -1892,7 +1893,7 @@ extern "C" __attribute__((visibility("default"))) int dn_debug_choice(const char
         snprintf(buf, (size_t)capacity, "blocks=%ld launched=%d", blocks, (int)(blocks < (1L << 30)));
         return DN_OK;
     }
-    if (f == "expdw") {
+    if (f == "expdw" || f == "expdw_whole") {
         DN_REQUIRE(nd == 12 && d[0] > 0 && d[1] > 0 && d[2] > 0 && d[6] >= 1 && d[7] >= 1, "dn_debug_choice: expdw takes n h w cin cexp cout k stride act1 act2 has_res pool");
         ExpDwArgs a{};
         a.x = a.wd = dummy_h; a.bd = dummy_f; a.pool = d[11] ? dummy_out : nullptr;
@@ -1903,6 +1904,7 @@ extern "C" __attribute__((visibility("default"))) int dn_debug_choice(const char
         a.act1 = a.w1 ? (int)d[8] : 0; a.act2 = (int)d[9]; a.has_res = (int)d[10]; a.xq = xcd_images_per_group(a.n);
         DN_REQUIRE(a.Ho > 0 && a.Wo > 0, "dn_debug_choice: expdw with an empty output");
         const ExpDwChoice c = expdw_choose(a, false);
+        if (f == "expdw_whole") { snprintf(buf, (size_t)capacity, "whole=%d lds=%zu", (int)c.whole, c.whole ? c.lds_w : (size_t)0); return DN_OK; }
         static const char* const bodies[] = {"none", "direct", "rows", "tiled", "tiled"};       // NONE, DIRECT, ROWS, ONE_PERSIST, TILED
         snprintf(buf, (size_t)capacity, "body=%s band=%d label=%s tile=%dx%d", bodies[c.body], c.band, c.label, c.oh, c.ow);
         return DN_OK;

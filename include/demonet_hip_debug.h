@@ -56,6 +56,8 @@ DN_API int dn_debug_stem(const float* img_dev, const float* w_dev, const float* 
  *               workgroup; body=rows: the row-reuse body of expdw_rows.hip, band= its output rows per wave; body=tiled: the bodies of expdw.hip;
  *               body=none: no body takes it; label= what the launch notes, whichever body runs; tile= the output tile <oh>x<ow> of the tiled
  *               bodies; reads DN_EXPDW_DIRECT / DN_EXPDW_DIRECT_BAND / DN_EXPDW_ROWS / DN_EXPDW_ROWS_BAND / DN_EXPDW_PERSIST / DN_EXPDW_ONE)
+ *   "expdw_whole" the same twelve numbers      (a flag of body=tiled that "expdw" does not show: whole= the phases are walked once over the whole
+ *               expanded width, expdw_whole.hip; lds= that form's LDS bytes, 0 without it; reads DN_EXPDW_WHOLE beside the knobs above)
  * 0 on success. */
 DN_API int dn_debug_choice(const char* family, const int64_t* dims, int ndims, char* buf, int capacity);
 
