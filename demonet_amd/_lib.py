@@ -57,6 +57,11 @@ class TrackParams(C.Structure):
                 ("track_buffer", C.c_int32), ("class_agnostic", C.c_int32), ("max_tracks", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TrackAppearanceParams(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("alpha", C.c_float), ("appearance_thresh", C.c_float), ("proximity_thresh", C.c_float),
+                ("emb_fp16", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class ZoneConfig(C.Structure):
     _fields_ = [("n_lines", C.c_int32), ("lines", C.c_float * 4 * 16), ("n_zones", C.c_int32), ("nv", C.c_int32 * 16),
                 ("verts", C.c_float * 2 * 16 * 16), ("reserved", C.c_int32 * 2)]
@@ -149,6 +154,12 @@ _SIGNATURES = {
     "dn_track_state_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "dn_track_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dn_track_update": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(TrackParams), C.c_void_p, C.c_size_t] + [C.c_void_p] * 8),
+    "dn_track_feature_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dn_track_appearance_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "dn_track_feature_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dn_track_update_appearance": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(TrackParams), C.POINTER(TrackAppearanceParams),
+                                             C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_size_t] + [C.c_void_p] * 8),
     "dn_zone_state_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "dn_zone_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dn_zone_update": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,

@@ -210,6 +210,31 @@ def track_frames(model, batch: FrameBatch, tracker, analytics=None):
     return with_analytics(tracker.update(boxes, scores, labels, counts), analytics)
 
 
+def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder, analytics=None):
+    """SSD.track_frames_appearance (see there)."""
+    from .crops import ObjectCropper
+    from .track import AppearanceTracker, with_analytics
+    if model.training:
+        raise ValueError("track_frames_appearance: the model must be in eval mode")
+    if not isinstance(tracker, AppearanceTracker):
+        raise ValueError("track_frames_appearance: tracker must be an AppearanceTracker, got {}".format(type(tracker)))
+    if not isinstance(cropper, ObjectCropper):
+        raise ValueError("track_frames_appearance: cropper must be an ObjectCropper, got {}".format(type(cropper)))
+    if not callable(embedder):
+        raise ValueError("track_frames_appearance: embedder must be callable, got {}".format(type(embedder)))
+    if analytics is not None:
+        from .zones import check_analytics
+        check_analytics(analytics, tracker, "track_frames_appearance")
+    boxes, scores, labels, counts = forward_frames(model, batch)
+    select = scores >= tracker.params.track_thresh          # the HIGH rows: the ones whose appearance the step uses (a device op, no wait)
+    patches, index, _ = cropper(batch, boxes, counts, select)
+    emb = embedder(patches)
+    if not isinstance(emb, Tensor) or tuple(emb.shape) != (cropper.capacity, tracker.dim):
+        raise ValueError("track_frames_appearance: the embedder must return [{}, {}], got {}".format(
+            cropper.capacity, tracker.dim, tuple(emb.shape) if isinstance(emb, Tensor) else type(emb)))
+    return with_analytics(tracker.update(boxes, scores, labels, counts, emb.contiguous(), index), analytics)
+
+
 # ---------------------------------------------------------------------------------------------------------------- regions (DESIGN 4q)
 def region_records(regions: Sequence, sizes: Sequence[Tuple[int, int]], n: int):
     """The validated dn_region records of `regions` -- (frame, x0, y0, w, h[, hflip]) tuples -- against sizes[frame] = (height, width), as

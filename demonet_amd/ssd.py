@@ -419,6 +419,14 @@ class SSD(_Tracked):
         from .frames import track_frames
         return track_frames(self, batch, tracker, analytics)
 
+    def track_frames_appearance(self, batch, tracker, cropper, embedder, analytics=None):
+        """`track_frames` with appearance, nothing leaving the device: forward_frames; cropper(batch, boxes, counts, select) with
+        select = scores >= the tracker's track_thresh, built on the device; embedder(patches), any callable that returns a [capacity, dim] fp16
+        or fp32 device tensor (the re-identification model: not part of this package); tracker.update(..., embeddings, cropper.index) for a
+        track.AppearanceTracker; then the analytics as in `track`. Returns what ByteTracker.update returns."""
+        from .frames import track_frames_appearance
+        return track_frames_appearance(self, batch, tracker, cropper, embedder, analytics)
+
     def forward_regions(self, batch, table, packed: Optional[Tensor] = None):
         """The forward on REGIONS of video surfaces (demonet_amd/frames.py): table is a frames.RegionTable of n (frame, x0, y0, w, h[,
         hflip]) rectangles of the FrameBatch's frames; network image i is rectangle i, mirrored left-right when flagged, resized to the network

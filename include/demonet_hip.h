@@ -643,6 +643,72 @@ DN_API int dn_track_update(const float* boxes_dev, const float* scores_dev, cons
                            int64_t* labels_out_dev, int64_t* ids_out_dev, int32_t* det_out_dev, int32_t* counts_out_dev, int64_t* det_ids_out_dev,
                            void* stream);
 
+/* Appearance association in the tracker (csrc/trackapp.hip): dn_track_update_appearance is dn_track_update with the appearance term of
+ * BoT-SORT (Aharon et al. 2022) -- cosine distance / 2, an appearance threshold, a proximity mask, min(d_iou, d_emb), an exponentially smoothed
+ * unit-norm feature per track -- fused into the pair value. demonet_amd/track.py (AppearanceTracker, SSD.track_frames_appearance) is the caller;
+ * tests/track_appearance_ref.py restates these sentences. Every argument of dn_track_update keeps its meaning, and the tracker's state block keeps
+ * its layout: dn_zone_update and the cropper read it as before.
+ * Inputs beside dn_track_update's, in DEVICE memory: emb_dev [E][dim], fp32 or (params->emb_fp16) fp16, and emb_index_dev [E][8] int32 -- the
+ * cropper's index table as it lies: word 0 the stream or -1, word 1 the row; the other words are not read. NONE OF THEM IS TRUSTED: an index row
+ * whose stream is outside 0 .. streams - 1 or whose row is outside 0 .. n - 1 (n = min(max(counts[stream], 0), d)) is ignored; if several index
+ * rows name the same (stream, row), the highest slot e wins (an integer maximum, so the order in which the device visits them does not
+ * matter), whether or not that slot's embedding is present. An embedding is ABSENT when an element is not finite or when its norm -- sqrt of
+ * the fp32 sum of the fp32 squares -- is 0 or not finite. A row HAS AN EMBEDDING when a winning slot names it and that slot's embedding is present.
+ * Normalised rows: en[e][k] = fp16(x[e][k] / norm_e), the fp32 quotient rounded to nearest even; the rows of absent embeddings are 0. (The order
+ * of the norm's sum is the implementation's and fixed: the same bits on every run.)
+ * Track features, features_dev, dn_track_feature_bytes(streams, max_tracks, dim) bytes, 16-byte aligned: per stream Tp (1 + dim) 4-byte words,
+ * streams back to back: int32 valid [Tp], then fp32 feature [Tp][dim]. The values of a slot whose flag is 0 mean nothing. dn_track_feature_reset
+ * zeroes the streams b with which_dev[b] != 0 (NULL: all); a new buffer must be reset before its first step, and a stream restarted with
+ * dn_track_reset must be reset here too. A slot that is free has valid = 0.
+ * Similarity: S[b][slot][row] = sum_k fp16(feature[slot][k]) * en[e(row)][k], fp16 operands (the feature rounded to nearest even), fp32
+ * accumulation on the matrix cores, from the features as the step found them. S is [streams][Tp][d] fp32; all of it is written in every step with
+ * embeddings, an entry whose slot has valid = 0 or whose row has no embedding as 0 (such an entry is never used).
+ * The pair value v of stages 1 and 3, fp32, one rounding per operation: u = the IoU of dn_track_update. If the track's slot has valid != 0 and the
+ * row has an embedding: h = (1 - S) * 0.5, e = h < 0 ? 0 : h (a NaN stays); appearance is ADMISSIBLE when e <= appearance_thresh and
+ * 1 - u <= proximity_thresh (a NaN never is); v = admissible ? (u > 1 - e ? u : 1 - e) : u. Otherwise, and always in stage 2 (the LOW rows:
+ * IoU alone, as published), v = u. Everything else is dn_track_update's text with v in place of u: the strict gates v > 1 - thresh, the labels,
+ * the total order (v descending, slot ascending, row ascending), greedy, new tracks, ids, removal, outputs. With proximity_thresh = 1 a pair with
+ * an empty intersection (u = 0) can match by appearance alone: a lost track is found again without overlap.
+ * The features after the step: a track that STARTS from a row with an embedding takes feature = float(en[e]) and valid = 1, from a row without
+ * one valid = 0. A MATCH (any stage) with a row that has an embedding: with valid != 0, s[k] = alpha * s[k] + (1 - alpha) * float(en[e][k])
+ * (1 - alpha: one fp32 subtraction), then s /= |s| (the fp32 norm as above; a norm that is 0 or not finite clears valid); with valid = 0 a plain
+ * start. A match with a row without an embedding leaves the feature alone. A slot that is freed (steps 6 and 8) gets valid = 0.
+ * With no row that has an embedding -- or with E = 0, emb_dev = emb_index_dev = NULL, when the workspace is not touched and may be NULL -- the
+ * step's outputs and state equal dn_track_update's bit for bit.
+ * The workspace, dn_track_appearance_workspace_bytes(streams, max_tracks, d, E, dim) bytes, 16-byte aligned; its parts in this order, each rounded
+ * up to a multiple of 16 bytes: en [E][dim] fp16, present [E] int32, map [streams][d] int32 (the winning slot of the row or -1),
+ * S [streams][Tp][d] fp32. en, S, present and map are outputs a caller may read after the step.
+ * params and app are HOST memory, read during the call only. Limits: dn_track_update's, E 0 .. 8192, dim a multiple of 32 in 32 .. 512:
+ * DN_E_UNSUPPORTED beyond them (the two size functions then return 0; dn_track_appearance_workspace_bytes also for E = 0). DN_E_INVALID for what
+ * dn_track_update refuses, a null app or features, dim < 1, E < 0, alpha not a number in 0 .. 1, a threshold that is NaN or negative, emb_fp16 not 0
+ * or 1, non-zero reserved words, E = 0 with a non-null emb or emb_index, E > 0 with a null emb, emb_index or workspace, features / emb / emb_index /
+ * workspace not 16-byte aligned. DN_E_WORKSPACE for state_bytes, feature_bytes or (E > 0) workspace_bytes below their size functions. Every error
+ * is raised before anything is enqueued. A step with embeddings enqueues four graph nodes (a fill of the map, the norms, the similarity, the
+ * step), one without embeddings the step alone; no device memory is allocated, no host synchronisation, can be captured; no float atomics;
+ * deterministic (the same bits on every run, S included). */
+typedef struct dn_track_appearance_params {   /* 32 bytes, HOST memory */
+    int32_t dim;                              /* a multiple of 32 in 32 .. 512 */
+    float   alpha;                            /* the feature's smoothing, 0 .. 1: 0.9 */
+    float   appearance_thresh;                /* on e = (1 - cosine) / 2: 0.25 */
+    float   proximity_thresh;                 /* on 1 - IoU: 0.5; 1 lets appearance match without overlap */
+    int32_t emb_fp16;                         /* 0: emb_dev is fp32, 1: fp16 */
+    int32_t reserved[3];                      /* 0 */
+} dn_track_appearance_params;
+#if defined(__cplusplus)
+static_assert(sizeof(dn_track_appearance_params) == 32, "dn_track_appearance_params is 32 bytes");
+#else
+_Static_assert(sizeof(dn_track_appearance_params) == 32, "dn_track_appearance_params is 32 bytes");
+#endif
+DN_API size_t dn_track_feature_bytes(int streams, int max_tracks, int dim);
+DN_API size_t dn_track_appearance_workspace_bytes(int streams, int max_tracks, int d, int E, int dim);
+DN_API int dn_track_feature_reset(void* features_dev, int streams, int max_tracks, int dim, const uint8_t* which_dev, void* stream);
+DN_API int dn_track_update_appearance(const float* boxes_dev, const float* scores_dev, const int64_t* labels_dev, const int32_t* counts_dev,
+                                      int streams, int d, const dn_track_params* params, const dn_track_appearance_params* app,
+                                      const void* emb_dev, const int32_t* emb_index_dev, int E, void* state_dev, size_t state_bytes,
+                                      void* features_dev, size_t feature_bytes, void* workspace_dev, size_t workspace_bytes,
+                                      float* boxes_out_dev, float* scores_out_dev, int64_t* labels_out_dev, int64_t* ids_out_dev,
+                                      int32_t* det_out_dev, int32_t* counts_out_dev, int64_t* det_ids_out_dev, void* stream);
+
 /* Line-crossing and zone analytics behind the tracker (csrc/zones.hip): per stream up to 16 directed lines and 16 polygon zones;
  * counters and a short event list accumulate on the device, ONE more small launch per frame step. demonet_amd/zones.py (ZoneAnalytics) is the
  * caller. dn_zone_update runs after dn_track_update on the same stream and READS the tracker's state as documented above (the header words and the
