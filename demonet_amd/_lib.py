@@ -73,6 +73,11 @@ class CropParams(C.Structure):
                 ("capacity", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class MotionParams(C.Structure):
+    _fields_ = [("max_h", C.c_int32), ("max_w", C.c_int32), ("block", C.c_int32), ("radius", C.c_int32), ("min_texture", C.c_int32),
+                ("min_blocks", C.c_int32), ("mask_thresh", C.c_float), ("reserved", C.c_int32)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("n_tensors", C.c_int32), ("n_ops", C.c_int32),
                 ("tensors", C.POINTER(TensorDesc)), ("ops", C.POINTER(OpDesc)),
@@ -167,6 +172,11 @@ _SIGNATURES = {
     "dn_crop_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "dn_crop_objects": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(CropParams),
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dn_motion_state_bytes": (C.c_size_t, [C.c_int, C.POINTER(MotionParams)]),
+    "dn_motion_reset": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(MotionParams), C.c_void_p, C.c_void_p]),
+    "dn_motion_estimate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(MotionParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dn_track_compensate": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 # include/demonet_hip_debug.h: test support beside the boundary (not part of EXPORTS, which mirrors demonet_hip.h)

@@ -196,7 +196,7 @@ def forward_frames(model, batch: FrameBatch, packed=None):
     return b["outs"]
 
 
-def track_frames(model, batch: FrameBatch, tracker, analytics=None):
+def track_frames(model, batch: FrameBatch, tracker, analytics=None, motion=None):
     """SSD.track_frames (see there)."""
     from .track import ByteTracker, with_analytics
     if model.training:
@@ -206,11 +206,16 @@ def track_frames(model, batch: FrameBatch, tracker, analytics=None):
     if analytics is not None:
         from .zones import check_analytics
         check_analytics(analytics, tracker, "track_frames")
+    if motion is not None:
+        from .motion import check_motion, compensated
+        check_motion(motion, tracker, batch, "track_frames")
     boxes, scores, labels, counts = forward_frames(model, batch)
+    if motion is not None:
+        compensated(motion, tracker, batch, boxes, scores, counts)
     return with_analytics(tracker.update(boxes, scores, labels, counts), analytics)
 
 
-def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder, analytics=None):
+def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder, analytics=None, motion=None):
     """SSD.track_frames_appearance (see there)."""
     from .crops import ObjectCropper
     from .track import AppearanceTracker, with_analytics
@@ -225,7 +230,12 @@ def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder
     if analytics is not None:
         from .zones import check_analytics
         check_analytics(analytics, tracker, "track_frames_appearance")
+    if motion is not None:
+        from .motion import check_motion, compensated
+        check_motion(motion, tracker, batch, "track_frames_appearance")
     boxes, scores, labels, counts = forward_frames(model, batch)
+    if motion is not None:
+        compensated(motion, tracker, batch, boxes, scores, counts)
     select = scores >= tracker.params.track_thresh          # the HIGH rows: the ones whose appearance the step uses (a device op, no wait)
     patches, index, _ = cropper(batch, boxes, counts, select)
     emb = embedder(patches)

@@ -323,7 +323,7 @@ def detect_sliced_frames(model, batch, tile=None, overlap: float = 0.25, full_im
     return [{"boxes": boxes[g, :c], "scores": scores[g, :c], "labels": labels[g, :c]} for g, c in enumerate(cnt)]
 
 
-def track_sliced_frames(model, batch, tracker, slicer: FrameSlicer, analytics=None):
+def track_sliced_frames(model, batch, tracker, slicer: FrameSlicer, analytics=None, motion=None):
     """SSD.track_sliced_frames (see there)."""
     from .track import ByteTracker, MAX_D as TRACK_MAX_D, with_analytics
     if not isinstance(tracker, ByteTracker):
@@ -335,4 +335,10 @@ def track_sliced_frames(model, batch, tracker, slicer: FrameSlicer, analytics=No
     if analytics is not None:
         from .zones import check_analytics
         check_analytics(analytics, tracker, "track_sliced_frames")
-    return with_analytics(tracker.update(*slicer(batch)), analytics)
+    if motion is None:
+        return with_analytics(tracker.update(*slicer(batch)), analytics)
+    from .motion import check_motion, compensated
+    check_motion(motion, tracker, batch, "track_sliced_frames")
+    boxes, scores, labels, counts = slicer(batch)
+    compensated(motion, tracker, batch, boxes, scores, counts)
+    return with_analytics(tracker.update(boxes, scores, labels, counts), analytics)

@@ -413,19 +413,21 @@ class SSD(_Tracked):
         from .frames import forward_frames
         return forward_frames(self, batch, packed)
 
-    def track_frames(self, batch, tracker, analytics=None):
+    def track_frames(self, batch, tracker, analytics=None, motion=None):
         """`track` on top of forward_frames: frame b of the FrameBatch is the current frame of stream b. Returns what ByteTracker.update returns;
-        analytics as in `track`."""
+        analytics as in `track`. motion: a motion.MotionCompensator for a moving camera: forward -> motion.estimate(batch, that
+        frame's detections) -> tracker.compensate -> update; None (the default): exactly the calls above."""
         from .frames import track_frames
-        return track_frames(self, batch, tracker, analytics)
+        return track_frames(self, batch, tracker, analytics, motion)
 
-    def track_frames_appearance(self, batch, tracker, cropper, embedder, analytics=None):
+    def track_frames_appearance(self, batch, tracker, cropper, embedder, analytics=None, motion=None):
         """`track_frames` with appearance, nothing leaving the device: forward_frames; cropper(batch, boxes, counts, select) with
         select = scores >= the tracker's track_thresh, built on the device; embedder(patches), any callable that returns a [capacity, dim] fp16
         or fp32 device tensor (the re-identification model: not part of this package); tracker.update(..., embeddings, cropper.index) for a
-        track.AppearanceTracker; then the analytics as in `track`. Returns what ByteTracker.update returns."""
+        track.AppearanceTracker; then the analytics as in `track`. Returns what ByteTracker.update returns. motion: as in `track_frames`
+        (estimate and compensate run behind the forward, in front of the crops)."""
         from .frames import track_frames_appearance
-        return track_frames_appearance(self, batch, tracker, cropper, embedder, analytics)
+        return track_frames_appearance(self, batch, tracker, cropper, embedder, analytics, motion)
 
     def forward_regions(self, batch, table, packed: Optional[Tensor] = None):
         """The forward on REGIONS of video surfaces (demonet_amd/frames.py): table is a frames.RegionTable of n (frame, x0, y0, w, h[,
@@ -452,12 +454,12 @@ class SSD(_Tracked):
         from .fusion import detect_tta_frames
         return detect_tta_frames(self, batch, fuse, thresh, skip_thresh)
 
-    def track_sliced_frames(self, batch, tracker, slicer, analytics=None):
+    def track_sliced_frames(self, batch, tracker, slicer, analytics=None, motion=None):
         """Video -> tiles -> merge -> ByteTrack without a host wait per frame step: tracker.update(*slicer(batch)) for a sliced.FrameSlicer of
         this model (frame g of the batch is the current frame of stream g). Returns what ByteTracker.update returns; analytics as in `track`.
-        ValueError when detections_per_img exceeds the tracker's 512 rows."""
+        ValueError when detections_per_img exceeds the tracker's 512 rows. motion: as in `track_frames`, with the merged detections."""
         from .sliced import track_sliced_frames
-        return track_sliced_frames(self, batch, tracker, slicer, analytics)
+        return track_sliced_frames(self, batch, tracker, slicer, analytics, motion)
 
     def crop_objects(self, batch, cropper, boxes, counts, select=None):
         """The objects of the frames as fixed-size normalised patches for a second model, on the device (demonet_amd/crops.py):

@@ -107,6 +107,20 @@ class ByteTracker:
                                                   *[p(o.data_ptr()) for o in outs], self._stream(stream)), "dn_track_update")
         return outs
 
+    def compensate(self, motion: Tensor, stream=None):
+        """Camera-motion compensation: warp the state of every stream b with motion[b] = (s, tx, ty, ok), ok != 0, by x' = s x + tx,
+        y' = s y + ty -- the centres, the heights, their velocities and covariances (include/demonet_hip.h, dn_track_compensate). motion:
+        [B, 4] fp32 on the tracker's device, what motion.MotionCompensator.estimate returns for the frame whose update comes next; a stream
+        whose ok is 0 is not written. One launch, no device-to-host copy."""
+        if not isinstance(motion, Tensor) or tuple(motion.shape) != (self.streams, 4) or motion.dtype != torch.float32 or not motion.is_contiguous() \
+                or motion.device != self.device:
+            raise ValueError("ByteTracker.compensate: motion must be a contiguous fp32 [{}, 4] tensor on {}, got {}".format(
+                self.streams, self.device, "{} {} on {}".format(motion.dtype, tuple(motion.shape), motion.device) if isinstance(motion, Tensor)
+                else type(motion)))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().dn_track_compensate(C.c_void_p(self.state.data_ptr()), self.state.numel(), self.streams, self.max_tracks,
+                                                      C.c_void_p(motion.data_ptr()), self._stream(stream)), "dn_track_compensate")
+
     def _check_step(self, boxes, scores, labels, counts):
         """What update checks before anything reaches the device -> (B, d, the output tensors of that d)."""
         if not isinstance(scores, Tensor) or scores.dim() != 2:

@@ -827,6 +827,77 @@ DN_API int dn_crop_objects(const dn_frame* frames_dev, int format, int color,
                            const dn_crop_params* params, void* patches_out_dev, int32_t* index_out_dev, int32_t* totals_out_dev,
                            void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Camera-motion compensation for the trackers (csrc/motion.hip): the third part of BoT-SORT (Aharon et al. 2022). The trackers' filter
+ * is constant-velocity in image coordinates, which is right for a fixed camera only; dn_motion_estimate measures the global motion of the image
+ * between a stream's previous and current frame from the luma of the surfaces, and dn_track_compensate applies it to the tracker's state in front
+ * of that frame's dn_track_update. demonet_amd/motion.py (MotionCompensator) and ByteTracker.compensate are the callers; tests/motion_ref.py
+ * restates these sentences in numpy.
+ * The model, per stream and frame step, previous frame -> current frame: x' = s x + tx, y' = s y + ty -- translation and isotropic scale. Rotation
+ * is deliberately left out: the filter is kept as four independent 2 x 2 blocks (dn_track_update), and only a transform that does not mix cx with cy
+ * preserves that structure.
+ * a. The luma thumbnail of a frame of W x H pixels, with (TH, TW) = (max_h, max_w) the capacity: k = the smallest integer >= 1 with
+ *    floor(W / k) <= TW and floor(H / k) <= TH; the thumbnail is th x tw = floor(H / k) x floor(W / k); pixel (i, j) is the rounded integer mean
+ *    (sum + floor(k k / 2)) / (k k) (integer division) of the 8-bit luma of the frame pixels x = k i .. k i + k - 1, y = k j .. k j + k - 1. The
+ *    remainder columns and rows at the right and the bottom are ignored. Luma: NV12 / I420 the Y byte as it lies (no range expansion); RGB24 /
+ *    BGR24 (77 R + 150 G + 29 B + 128) >> 8. k is at most 4096 (k k 255 < 2^32: the sum is a uint32); a frame beyond that has no blocks.
+ * b. Block vectors. With B = block, r = radius: if tw < B + 2 r or th < B + 2 r the frame has no blocks; otherwise nbx = floor((tw - 2 r) / B) by
+ *    nby = floor((th - 2 r) / B) blocks, block n = nbx * by_index + bx_index at the corner (bx, by) = (r + B bx_index, r + B by_index) of the CURRENT
+ *    thumbnail. It is searched in the PREVIOUS thumbnail over all (dx, dy) in [-r, r]^2: SAD(dx, dy) = the sum over the block's pixels (i, j) of
+ *    |cur(bx + i, by + j) - prev(bx + dx + i, by + dy + j)|. The winner is the minimum of the total order (SAD, dx dx + dy dy, dy, dx). A block is
+ *    invalid if (1) its texture sum |p - m| over its pixels p, m = (sum p + B B / 2) / (B B), is below min_texture, or (2) its centre lies inside a
+ *    masking detection box: with cx = (float)(k (bx + B / 2)) - 0.5f and cy likewise, a row j < min(max(counts[b], 0), d) with score >= mask_thresh
+ *    (a NaN score masks nothing), four finite coordinates and x1 <= cx < x2 and y1 <= cy < y2. boxes, scores, counts all NULL: no masking.
+ * c. The fit. mdx, mdy = the lower medians (rank floor((valid - 1) / 2) in ascending order) of the valid blocks' dx and dy; the inliers are the
+ *    valid blocks with max(|dx - mdx|, |dy - mdy|) <= 2. A block centre u = (bx + B / 2, by + B / 2) of the current thumbnail corresponds to u + d in
+ *    the previous one: the fitted pairs are (x, y) = u + d -> (x', y') = u. Over the inliers, exact int64 sums n, Sx, Sy, Sx', Sy', Sqq = sum (x x +
+ *    y y), Sxx = sum (x x' + y y'); num = n Sxx - Sx Sx' - Sy Sy', den = n Sqq - Sx Sx - Sy Sy, each converted to float64 once; s = num / den;
+ *    tu = (Sx' - s Sx) / n, tv = (Sy' - s Sy) / n in float64 in that order; to frame coordinates tx = k tu + ((1 - s) (k - 1)) / 2, ty likewise,
+ *    float64; s, tx, ty are then rounded to fp32 once.
+ *    The step is NOT ok, and the motion is the identity (1, 0, 0), when: it is the stream's first frame since the reset; the frame's size differs
+ *    from the stored thumbnail's frame; valid < min_blocks; 2 inliers < valid; den = 0; s < 0.8 or s > 1.25 (the float64 s). In the first two cases
+ *    no block is searched: every vector row is 0 and valid = inliers = 0. The new thumbnail replaces the stored one in every case.
+ * Outputs: motion_out [n][4] fp32 (s, tx, ty, ok = 1 | 0); stats_out [n][4] int32 (blocks, valid, inliers, k); vectors_out [n][max_blocks][4] int32
+ * (dx, dy, sad, valid) or NULL, max_blocks = floor((TW - 2 r) / B) floor((TH - 2 r) / B), rows at or beyond the frame's blocks 0.
+ * The state, dn_motion_state_bytes(streams, params) bytes, 16-byte aligned, per stream 16 + 16 max_blocks + 2 TH TWp bytes, TWp = TW rounded up to
+ * a multiple of 16, streams back to back: int32 parity, have, height, width (of the stored thumbnail's frame); the step's vectors [max_blocks][4]
+ * int32; two thumbnails of TH rows of TWp bytes. Thumbnail `parity` is the stored (previous) one; a step writes the other and flips the word last,
+ * which is why the step's arguments never change and a captured graph replays. Only th x tw bytes of a thumbnail mean anything. dn_motion_reset
+ * zeroes the streams b with which_dev[b] != 0 (NULL: all); a new state must be reset before its first step.
+ * d. dn_track_compensate: for every stream b with motion[b].ok != 0 and every slot whose state is not free (dn_track_update's state block; its
+ *    layout does not change), fp32, one rounding per operation, no contraction, s2 = s * s: cx: x = s * x + tx (one multiply, then one add);
+ *    cy: the same with ty; h: x = s * x; a: untouched; for cx, cy and h: v = s * v, Pxx = Pxx * s2, Pxv = Pxv * s2, Pvv = Pvv * s2. A stream whose
+ *    step is not ok is not written at all. It runs BEFORE that frame's dn_track_update: F commutes with the transform, so warp-then-predict equals
+ *    BoT-SORT's predict-then-warp in exact arithmetic (Q is then computed from the already scaled h: a rounding-level difference). Zone geometry
+ *    (dn_zone_update) is in image coordinates and is not warped.
+ * TRUST BOUNDARY: the frame table is trusted as for dn_forward_frames; box values are not (they are only compared).
+ * Limits: block 8 | 16, radius 1 .. 16, capacity sides block + 2 radius .. 512, n and streams 1 .. 65535, d 1 .. 512 with masking, max_tracks
+ * 1 .. 256: DN_E_UNSUPPORTED beyond the capacity, stream, d and max_tracks limits and for an unknown format (dn_motion_state_bytes then returns 0).
+ * DN_E_INVALID for null pointers (the optional ones excepted), some but not all of boxes / scores / counts, non-positive sizes, a bad block or
+ * radius, min_texture < 0, min_blocks < 1, a NaN mask_thresh, a non-zero reserved word, the state, boxes, motion, stats or vectors not 16-byte
+ * aligned. DN_E_WORKSPACE for state_bytes below the state's size. Every error is raised before anything is launched. dn_motion_estimate is three
+ * launches (thumbnails, block match, fit), dn_track_compensate one; asynchronous on `stream`, no host synchronisation, can be captured (the frame
+ * table is read when the kernels run); no float atomics; deterministic (the same bits on every run). params is HOST memory, read during the call. */
+typedef struct dn_motion_params {    /* 32 bytes, HOST memory */
+    int32_t max_h, max_w;            /* the thumbnail capacity (TH, TW): 144, 256 */
+    int32_t block;                   /* 8 | 16 */
+    int32_t radius;                  /* 1 .. 16 */
+    int32_t min_texture;             /* >= 0: 2 * block * block */
+    int32_t min_blocks;              /* >= 1: 8 */
+    float   mask_thresh;             /* 0.5 */
+    int32_t reserved;                /* 0 */
+} dn_motion_params;
+#ifdef __cplusplus
+static_assert(sizeof(dn_motion_params) == 32, "dn_motion_params is 32 bytes");
+#else
+_Static_assert(sizeof(dn_motion_params) == 32, "dn_motion_params is 32 bytes");
+#endif
+DN_API size_t dn_motion_state_bytes(int streams, const dn_motion_params* params);
+DN_API int dn_motion_reset(void* state_dev, size_t state_bytes, int streams, const dn_motion_params* params, const uint8_t* which_dev, void* stream);
+DN_API int dn_motion_estimate(const dn_frame* frames_dev, int n, int format, const dn_motion_params* params, const float* boxes_dev,
+                              const float* scores_dev, const int32_t* counts_dev, int d, void* state_dev, size_t state_bytes, float* motion_out_dev,
+                              int32_t* stats_out_dev, int32_t* vectors_out_dev, void* stream);
+DN_API int dn_track_compensate(void* track_state_dev, size_t track_state_bytes, int streams, int max_tracks, const float* motion_dev, void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
