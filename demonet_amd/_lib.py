@@ -17,6 +17,7 @@ DN_REGION_HFLIP = 1
 DN_SGD_CHUNK = 2048
 DN_SGD_MAX_GATE = 8
 DN_ZONE = dict(cross=1, enter=2, exit=3, vanish=4)
+DN_OSD_LABEL, DN_OSD_SCORE, DN_OSD_HIDE = 1, 2, 4
 
 
 class TensorDesc(C.Structure):
@@ -76,6 +77,20 @@ class CropParams(C.Structure):
 class MotionParams(C.Structure):
     _fields_ = [("max_h", C.c_int32), ("max_w", C.c_int32), ("block", C.c_int32), ("radius", C.c_int32), ("min_texture", C.c_int32),
                 ("min_blocks", C.c_int32), ("mask_thresh", C.c_float), ("reserved", C.c_int32)]
+
+
+class OsdStyle(C.Structure):
+    _fields_ = [("thickness", C.c_uint8), ("fill_alpha", C.c_uint8), ("pixelate", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint8 * 4)]
+
+
+class OsdColor(C.Structure):
+    _fields_ = [("color", C.c_uint8 * 3), ("text", C.c_uint8 * 3), ("reserved", C.c_uint8 * 2)]
+
+
+class OsdParams(C.Structure):
+    _fields_ = [("default_style", OsdStyle), ("n_colors", C.c_int32), ("color_by_id", C.c_int32), ("scale", C.c_int32), ("label_alpha", C.c_int32),
+                ("line_thickness", C.c_int32), ("zone_thickness", C.c_int32), ("zone_alpha", C.c_int32), ("line_color", C.c_uint8 * 3),
+                ("reserved0", C.c_uint8), ("zone_color", C.c_uint8 * 3), ("reserved1", C.c_uint8), ("reserved", C.c_int32 * 5)]
 
 
 class ModelDesc(C.Structure):
@@ -177,6 +192,9 @@ _SIGNATURES = {
     "dn_motion_estimate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(MotionParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                      C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dn_track_compensate": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dn_osd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dn_osd_paint": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+                     + [C.POINTER(OsdParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 # include/demonet_hip_debug.h: test support beside the boundary (not part of EXPORTS, which mirrors demonet_hip.h)

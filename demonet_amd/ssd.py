@@ -413,21 +413,24 @@ class SSD(_Tracked):
         from .frames import forward_frames
         return forward_frames(self, batch, packed)
 
-    def track_frames(self, batch, tracker, analytics=None, motion=None):
+    def track_frames(self, batch, tracker, analytics=None, motion=None, osd=None):
         """`track` on top of forward_frames: frame b of the FrameBatch is the current frame of stream b. Returns what ByteTracker.update returns;
         analytics as in `track`. motion: a motion.MotionCompensator for a moving camera: forward -> motion.estimate(batch, that
-        frame's detections) -> tracker.compensate -> update; None (the default): exactly the calls above."""
+        frame's detections) -> tracker.compensate -> update; None (the default): exactly the calls above. osd: an osd.Overlay: the
+        tracker's outputs -- and the analytics' lines and zones -- are painted INTO THE FRAMES as the step's last act, after the motion estimate
+        (and the crops) have read them; the return value does not change. THE PAINT MUST COME LAST: whatever reads the frames after it sees
+        painted pixels. None (the default): exactly the calls above."""
         from .frames import track_frames
-        return track_frames(self, batch, tracker, analytics, motion)
+        return track_frames(self, batch, tracker, analytics, motion, osd)
 
-    def track_frames_appearance(self, batch, tracker, cropper, embedder, analytics=None, motion=None):
+    def track_frames_appearance(self, batch, tracker, cropper, embedder, analytics=None, motion=None, osd=None):
         """`track_frames` with appearance, nothing leaving the device: forward_frames; cropper(batch, boxes, counts, select) with
         select = scores >= the tracker's track_thresh, built on the device; embedder(patches), any callable that returns a [capacity, dim] fp16
         or fp32 device tensor (the re-identification model: not part of this package); tracker.update(..., embeddings, cropper.index) for a
         track.AppearanceTracker; then the analytics as in `track`. Returns what ByteTracker.update returns. motion: as in `track_frames`
-        (estimate and compensate run behind the forward, in front of the crops)."""
+        (estimate and compensate run behind the forward, in front of the crops). osd: as in `track_frames` (the paint follows the crops)."""
         from .frames import track_frames_appearance
-        return track_frames_appearance(self, batch, tracker, cropper, embedder, analytics, motion)
+        return track_frames_appearance(self, batch, tracker, cropper, embedder, analytics, motion, osd)
 
     def forward_regions(self, batch, table, packed: Optional[Tensor] = None):
         """The forward on REGIONS of video surfaces (demonet_amd/frames.py): table is a frames.RegionTable of n (frame, x0, y0, w, h[,
@@ -454,12 +457,20 @@ class SSD(_Tracked):
         from .fusion import detect_tta_frames
         return detect_tta_frames(self, batch, fuse, thresh, skip_thresh)
 
-    def track_sliced_frames(self, batch, tracker, slicer, analytics=None, motion=None):
+    def track_sliced_frames(self, batch, tracker, slicer, analytics=None, motion=None, osd=None):
         """Video -> tiles -> merge -> ByteTrack without a host wait per frame step: tracker.update(*slicer(batch)) for a sliced.FrameSlicer of
         this model (frame g of the batch is the current frame of stream g). Returns what ByteTracker.update returns; analytics as in `track`.
-        ValueError when detections_per_img exceeds the tracker's 512 rows. motion: as in `track_frames`, with the merged detections."""
+        ValueError when detections_per_img exceeds the tracker's 512 rows. motion: as in `track_frames`, with the merged detections. osd: as in
+        `track_frames`."""
         from .sliced import track_sliced_frames
-        return track_sliced_frames(self, batch, tracker, slicer, analytics, motion)
+        return track_sliced_frames(self, batch, tracker, slicer, analytics, motion, osd)
+
+    def paint_frames(self, batch, overlay, boxes, scores, labels, counts, ids=None, zones=None):
+        """On-screen display (demonet_amd/osd.py): overlay.paint(batch, boxes, scores, labels, counts, ids, zones) for an osd.Overlay on
+        this model's device -- boxes, labels, lines, zones and redaction painted in place into the frames, in their own colour space, without a
+        device-to-host copy. Returns the overlay's stats [B, 4] int32. Paint last: later readers of the frames see the painted pixels."""
+        from .osd import paint_frames
+        return paint_frames(self, batch, overlay, boxes, scores, labels, counts, ids, zones)
 
     def crop_objects(self, batch, cropper, boxes, counts, select=None):
         """The objects of the frames as fixed-size normalised patches for a second model, on the device (demonet_amd/crops.py):

@@ -898,6 +898,109 @@ DN_API int dn_motion_estimate(const dn_frame* frames_dev, int n, int format, con
                               int32_t* stats_out_dev, int32_t* vectors_out_dev, void* stream);
 DN_API int dn_track_compensate(void* track_state_dev, size_t track_state_bytes, int streams, int max_tracks, const float* motion_dev, void* stream);
 
+/* On-screen display on the device (csrc/osd.hip): track boxes, class / id / score labels, counting lines, zone edges and redaction
+ * (pixelation, opaque fill) painted IN PLACE into the surfaces a dn_frame table names, in the surfaces' own colour space, without a box or an id
+ * visiting the host. demonet_amd/osd.py (Overlay) is the caller; tests/osd_ref.py restates these sentences in numpy.
+ * Surfaces. frames_dev: [n] dn_frame records (format: dn_forward_frames' codes); stream b paints frame b; width, height, planes and pitches come from
+ * the records in device memory. Colours are bytes in the surface's own space in logical order: (Y, U, V) for NV12 / I420, (R, G, B) for RGB24 /
+ * BGR24 -- the kernel swaps R and B for BGR24. The device never converts a colour; the caller does, once per palette (Python: Y = ((yr R + yg G +
+ * yb B + 2^13) >> 14) + yo, U = ((ur R + ug G + ub B + 2^13) >> 14) + 128, V likewise, >> arithmetic, clamped to 0 .. 255, every coefficient
+ * round(c 2^14) of the BT.601 / BT.709 forward matrix in limited (219/255, 224/255, yo = 16) or full range).
+ * One pixel, one owner. A pixel's value starts as the frame's value before the call; the primitives that cover the pixel are applied in the fixed
+ * order below, later ones over earlier ones. A blend is per component with an exact integer division: out = (a c + (255 - a) p + 127) / 255, a the
+ * alpha, c the colour, p the current value. In the 4:2:0 formats chroma sample (cx, cy) is governed by luma pixel (2 cx, 2 cy) (dn_forward_frames'
+ * (x >> 1, y >> 1)): U and V receive exactly the primitives that cover that pixel, in the same order with the same alpha. Odd frame sizes are
+ * legal. The bytes of uncovered pixels, every byte of a pitch gap and everything of a frame no primitive touches keep their value; a workgroup may
+ * store back the value it read for an uncovered payload byte of a 32 x 32 tile it owns, nowhere else.
+ * Order, per stream: 1. the lines and zone edges of the stream's dn_zone_config: lines ascending, then zones ascending with edges ascending;
+ * 2. the boxes, rows ascending, within a row pixelate, then fill, then outline; 3. the labels, rows ascending.
+ * Rows. boxes_dev [n][d][4] fp32, scores_dev [n][d] fp32, labels_dev [n][d] int64, ids_dev [n][d] int64 or NULL, counts_dev [n] int32: a tracker's
+ * outputs or raw detections. Row j is used iff j < min(max(counts[b], 0), d), its four coordinates are finite, its label lies in [0, n_labels) and its
+ * style has no DN_OSD_HIDE. Its rectangle: ix0 = floor(x1), iy0 = floor(y1), ix1 = ceil(x2), iy1 = ceil(y2), each clamped AS A FLOAT to [0, W]
+ * or [0, H] before the conversion to int; a row whose rectangle is empty (ix0 >= ix1 or iy0 >= iy1) is skipped. Its style is styles_dev[label], an
+ * 8-byte dn_osd_style (NULL table: params->default_style for every row); a thickness above 16 counts as 16, a pixelate block that is not 4, 8, 16
+ * or 32 as 0. Its colour is palette_dev[key % n_colors], key = the low 32 bits, unsigned, of the id when ids are given and params->color_by_id,
+ * else of the label; the palette holds n_colors (1 .. 256) dn_osd_color records.
+ *   outline, thickness t > 0: the rectangle minus the rectangle shrunk by t on every side; when the shrunk rectangle is empty the whole rectangle.
+ *     Opaque (the colour replaces the value).
+ *   fill: the rectangle, blended with the style's fill_alpha.
+ *   pixelate, block s: blocks are anchored at the frame origin. A covered pixel takes (sum + cnt / 2) / cnt (integer division) over its block
+ *     intersected with the frame, per plane (per channel for RGB); in 4:2:0 a governed chroma sample takes the mean of its (s/2) x (s/2) chroma
+ *     block intersected with the ceil-sized chroma plane. The sum is ALWAYS over the frame as it was before the call, never over painted values.
+ * Labels. A row whose style has DN_OSD_LABEL gets a text, built on the device: the class name names_dev[label] (16 bytes, NUL-padded, at most 15
+ * characters; a NULL table: no name); with ids, " #" and the id's decimal digits, or "?" for an id outside 0 .. 999 999 999; with DN_OSD_SCORE,
+ * " " p "%", p = (int) of v = score * 100.f + 0.5f clamped as a float to 0 .. 100, or "?" for a non-finite score. At most 31 characters. font_dev:
+ * [64][8] uint8, the glyphs of ASCII 32 .. 95, bit 7 - c of row byte r is column c; a lowercase letter takes the uppercase glyph, every other byte
+ * outside 32 .. 95 takes '?'. At scale k (1 .. 4) the label rectangle is 8 k len wide and 8 k high at left = ix0, top = iy0 - 8 k when iy0 >= 8 k,
+ * else iy0, cut at the frame's edges. Pixel (x, y) of it: column (x - left) / k, row (y - top) / k, character = column >> 3; a set glyph bit takes
+ * the palette entry's text colour, a clear one its colour, both blended with label_alpha.
+ * Segments. zone_config_dev: ZoneAnalytics' own [n] dn_zone_config, read where it lies, or NULL; n_lines, n_zones and nv are clamped as in
+ * dn_zone_update. Line i is A = (ax, ay) -> B = (bx, by); edge e of a zone is A = verts[e] -> B = verts[(e + 1) % nv]. A segment covers the pixel
+ * with centre p = (x + 0.5, y + 0.5) by this test in fp32, one rounding per operation, in this order: dx = bx - ax, dy = by - ay, L = dx*dx + dy*dy
+ * (L == 0 or not finite: the segment is skipped); t = ((px - ax)*dx + (py - ay)*dy) / L clamped to [0, 1]; qx = ax + t*dx, qy = ay + t*dy;
+ * ex = px - qx, ey = py - qy; covered iff ex*ex + ey*ey <= r*r, r = (float)thickness * 0.5f. Lines take line_color, zone edges zone_color, both
+ * blended with zone_alpha.
+ * Two launches. Launch 1, one workgroup per stream: validates the rows, makes the rectangles, formats the label
+ * bytes, compacts the live primitives in paint order, marks the 32 x 32 tiles (anchored at the origin) each primitive can touch -- rectangles
+ * exactly, segments by a bounding box grown by the radius -- and appends the marked tiles to one work list through one integer atomic per
+ * workgroup. Every tile is independent, so the list's order may vary without changing a byte. Launch 2, a fixed grid of persistent workgroups,
+ * walks the list: per tile it snapshots the planes into LDS before it writes anything (every pixelate block lies inside one tile: in place is
+ * race-free), paints each 2 x 2 luma quad with its chroma pair in one thread, and stores. Traffic is proportional to the tiles touched.
+ * The workspace, dn_osd_workspace_bytes(n, d, tile_capacity) bytes, 16-byte aligned. ITS FIRST 16 BYTES MUST BE ZERO BEFORE THE FIRST CALL: bytes
+ * 0 .. 7 are the tile counter (64 bits: no sum of tiles over the streams wraps), word 3 counts the finished workgroups of launch 2, whose last one
+ * clears both again and leaves word 2 int32 = the tiles the call marked (kept and dropped, saturated at 2^31 - 1). RECOVERY: when a call returns
+ * DN_E_HIP (a launch could not be enqueued), when a graph holding the call is abandoned half way, or when the memory is reused for anything else,
+ * zero the first 16 bytes again before the next call (an ordinary fill on the same stream); until then later calls would append behind stale
+ * entries and drop tiles. A frame is taken to have fewer than 2^31 tiles (the per-stream figures of stats_dev are int32).
+ * The work list, [tile_capacity] pairs of int32 (stream, ty * ceil(W / 32) + tx), starts at byte dn_osd_workspace_bytes(n, d, 0).
+ * tile_capacity of a call = (workspace_bytes - dn_osd_workspace_bytes(n, d, 0)) / 8; tiles beyond it are dropped, counted and never written.
+ * stats_dev [n][4] int32: rows painted, rows skipped (of the j < min(max(count, 0), d)), tiles touched, tiles dropped.
+ * TRUST BOUNDARY: the frame table is trusted as for dn_forward_frames (a frame wider than 2^21 pixels is not painted). Boxes, scores, labels, ids,
+ * counts, the zone config, the style bytes and the name bytes are NOT: whatever they hold, no access leaves the frames or the tables' sizes.
+ * DN_E_INVALID for null pointers (ids_dev, styles_dev, zone_config_dev excepted, and names_dev when styles_dev is given or the default style has no
+ * DN_OSD_LABEL), n, d or n_labels < 1, boxes / workspace / stats / zone config not 16-byte aligned, labels / ids / styles / palette not 8-byte,
+ * scores / counts not 4-byte aligned, scale outside 1 .. 4, line or zone thickness outside 1 .. 64, a default thickness above 16 or block not 0, 4,
+ * 8, 16, 32, n_colors outside 1 .. 256, an alpha outside 0 .. 255, non-zero reserved words, an unknown format. DN_E_UNSUPPORTED for d > 512 or
+ * n > 65535 (dn_osd_workspace_bytes then returns 0). DN_E_WORKSPACE for workspace_bytes below dn_osd_workspace_bytes(n, d, 1). Every error is raised
+ * before anything is enqueued. Asynchronous on `stream`, no host synchronisation, can be captured (every table is read when the kernels run); no
+ * float atomics; deterministic (the same bits on every run). params is HOST memory, read during the call. */
+enum { DN_OSD_LABEL = 1, DN_OSD_SCORE = 2, DN_OSD_HIDE = 4 };
+typedef struct dn_osd_style {        /* 8 bytes, DEVICE memory (styles_dev[n_labels]) and inside dn_osd_params */
+    uint8_t thickness;               /* outline, 0 .. 16 pixels; 0: none */
+    uint8_t fill_alpha;              /* 0: no fill .. 255: opaque */
+    uint8_t pixelate;                /* block: 0 (off), 4, 8, 16 or 32 */
+    uint8_t flags;                   /* DN_OSD_LABEL | DN_OSD_SCORE | DN_OSD_HIDE */
+    uint8_t reserved[4];
+} dn_osd_style;
+typedef struct dn_osd_color {        /* 8 bytes, DEVICE memory (palette_dev[n_colors]) */
+    uint8_t color[3];                /* surface space, logical order */
+    uint8_t text[3];                 /* the text's colour on it */
+    uint8_t reserved[2];
+} dn_osd_color;
+typedef struct dn_osd_params {       /* 64 bytes, HOST memory */
+    dn_osd_style default_style;      /* the style of every row when styles_dev is NULL */
+    int32_t n_colors;                /* 1 .. 256 */
+    int32_t color_by_id;             /* 0 | 1 */
+    int32_t scale;                   /* 1 .. 4: a character cell is 8 scale x 8 scale */
+    int32_t label_alpha;             /* 0 .. 255 */
+    int32_t line_thickness;          /* 1 .. 64 */
+    int32_t zone_thickness;          /* 1 .. 64 */
+    int32_t zone_alpha;              /* 0 .. 255, lines and zone edges */
+    uint8_t line_color[3], reserved0;
+    uint8_t zone_color[3], reserved1;
+    int32_t reserved[5];             /* 0 */
+} dn_osd_params;
+#ifdef __cplusplus
+static_assert(sizeof(dn_osd_params) == 64 && sizeof(dn_osd_style) == 8 && sizeof(dn_osd_color) == 8, "dn_osd_params is 64 bytes, its records 8");
+#else
+_Static_assert(sizeof(dn_osd_params) == 64 && sizeof(dn_osd_style) == 8 && sizeof(dn_osd_color) == 8, "dn_osd_params is 64 bytes, its records 8");
+#endif
+DN_API size_t dn_osd_workspace_bytes(int streams, int d, int tile_capacity);
+DN_API int dn_osd_paint(const dn_frame* frames_dev, int n, int format, const float* boxes_dev, const float* scores_dev, const int64_t* labels_dev,
+                        const int64_t* ids_dev, const int32_t* counts_dev, int d, const dn_osd_style* styles_dev, int n_labels,
+                        const uint8_t* names_dev, const dn_osd_color* palette_dev, const uint8_t* font_dev, const dn_zone_config* zone_config_dev,
+                        const dn_osd_params* params, void* workspace_dev, size_t workspace_bytes, int32_t* stats_dev, void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
