@@ -93,6 +93,15 @@ class OsdParams(C.Structure):
                 ("reserved0", C.c_uint8), ("zone_color", C.c_uint8 * 3), ("reserved1", C.c_uint8), ("reserved", C.c_int32 * 5)]
 
 
+class ComposeItem(C.Structure):
+    _fields_ = [("src", C.c_int32), ("sx0", C.c_int32), ("sy0", C.c_int32), ("sw", C.c_int32), ("sh", C.c_int32), ("dst", C.c_int32),
+                ("dx0", C.c_int32), ("dy0", C.c_int32), ("dw", C.c_int32), ("dh", C.c_int32), ("tile0", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ComposeHeader(C.Structure):
+    _fields_ = [("n_items", C.c_int32), ("n_tiles", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("n_tensors", C.c_int32), ("n_ops", C.c_int32),
                 ("tensors", C.POINTER(TensorDesc)), ("ops", C.POINTER(OpDesc)),
@@ -195,6 +204,8 @@ _SIGNATURES = {
     "dn_osd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "dn_osd_paint": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
                      + [C.POINTER(OsdParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "dn_compose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "dn_surface_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 # include/demonet_hip_debug.h: test support beside the boundary (not part of EXPORTS, which mirrors demonet_hip.h)

@@ -2,7 +2,7 @@
 
     python -m demonet_amd.build [--force]
 
-One object per .hip file (postprocess.hip, sliced.hip, evalmatch.hip, cocomatch.hip, augment.hip, optim.hip, fuse.hip, track.hip, trackapp.hip, zones.hip, crops.hip, motion.hip, osd.hip and detset.hip with -ffp-contract=off: decode/IoU must round like the
+One object per .hip file (postprocess.hip, sliced.hip, evalmatch.hip, cocomatch.hip, augment.hip, optim.hip, fuse.hip, track.hip, trackapp.hip, zones.hip, crops.hip, motion.hip, osd.hip, compose.hip and detset.hip with -ffp-contract=off: decode/IoU must round like the
 reference, the augmentation like its fp32 emulation, the SGD update like torch.optim.SGD, the box fusion, the tracker and its appearance step, the zone analytics, the object crops behind it, the camera-motion compensation and the on-screen display like their float32 restatements,
 and detset.hip, the ranking that merge and fusion share, is built like its two users),
 linked into one C-ABI shared library. In-tree output so the .so travels with the repo snapshot to the GPU box.
@@ -15,11 +15,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdemonet_hip.so")
-SOURCES = ["plan.hip", "pointwise.hip", "depthwise.hip", "dense.hip", "postprocess.hip", "expdw.hip", "expdw_direct.hip", "expdw_rows.hip", "expdw_whole.hip", "tail.hip", "convbig.hip", "pwdirect.hip", "loss.hip", "headfuse.hip", "headgrad.hip", "sliced.hip", "evalmatch.hip", "cocomatch.hip", "augment.hip", "optim.hip", "fuse.hip", "track.hip", "trackapp.hip", "detset.hip", "zones.hip", "crops.hip", "motion.hip", "osd.hip"]
+SOURCES = ["plan.hip", "pointwise.hip", "depthwise.hip", "dense.hip", "postprocess.hip", "expdw.hip", "expdw_direct.hip", "expdw_rows.hip", "expdw_whole.hip", "tail.hip", "convbig.hip", "pwdirect.hip", "loss.hip", "headfuse.hip", "headgrad.hip", "sliced.hip", "evalmatch.hip", "cocomatch.hip", "augment.hip", "optim.hip", "fuse.hip", "track.hip", "trackapp.hip", "detset.hip", "zones.hip", "crops.hip", "motion.hip", "osd.hip", "compose.hip"]
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs, not AGPRs -- the small-tile kernels otherwise spend a v_accvgpr_read per
 # accumulator value on the way to their epilogues (not for convbig.hip: its 256 x 256 tiles need the AGPR half of the file)
 VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
-EXTRA = {"postprocess.hip": ["-ffp-contract=off"], "sliced.hip": ["-ffp-contract=off"], "evalmatch.hip": ["-ffp-contract=off"], "cocomatch.hip": ["-ffp-contract=off"], "augment.hip": ["-ffp-contract=off"], "optim.hip": ["-ffp-contract=off"], "fuse.hip": ["-ffp-contract=off"], "track.hip": ["-ffp-contract=off"], "trackapp.hip": ["-ffp-contract=off"], "detset.hip": ["-ffp-contract=off"], "zones.hip": ["-ffp-contract=off"], "crops.hip": ["-ffp-contract=off"], "motion.hip": ["-ffp-contract=off"], "osd.hip": ["-ffp-contract=off"], "pwdirect.hip": VGPR_MFMA, "expdw_direct.hip": VGPR_MFMA, "expdw_rows.hip": VGPR_MFMA, "expdw_whole.hip": VGPR_MFMA, "pointwise.hip": VGPR_MFMA, "tail.hip": VGPR_MFMA, "depthwise.hip": VGPR_MFMA}
+EXTRA = {"postprocess.hip": ["-ffp-contract=off"], "sliced.hip": ["-ffp-contract=off"], "evalmatch.hip": ["-ffp-contract=off"], "cocomatch.hip": ["-ffp-contract=off"], "augment.hip": ["-ffp-contract=off"], "optim.hip": ["-ffp-contract=off"], "fuse.hip": ["-ffp-contract=off"], "track.hip": ["-ffp-contract=off"], "trackapp.hip": ["-ffp-contract=off"], "detset.hip": ["-ffp-contract=off"], "zones.hip": ["-ffp-contract=off"], "crops.hip": ["-ffp-contract=off"], "motion.hip": ["-ffp-contract=off"], "osd.hip": ["-ffp-contract=off"], "compose.hip": ["-ffp-contract=off"], "pwdirect.hip": VGPR_MFMA, "expdw_direct.hip": VGPR_MFMA, "expdw_rows.hip": VGPR_MFMA, "expdw_whole.hip": VGPR_MFMA, "pointwise.hip": VGPR_MFMA, "tail.hip": VGPR_MFMA, "depthwise.hip": VGPR_MFMA}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 COMMON = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
           "-fvisibility=hidden", "-fgpu-rdc" if False else "-fno-gpu-rdc"]

@@ -196,10 +196,11 @@ def forward_frames(model, batch: FrameBatch, packed=None):
     return b["outs"]
 
 
-def track_frames(model, batch: FrameBatch, tracker, analytics=None, motion=None, osd=None):
+def track_frames(model, batch: FrameBatch, tracker, analytics=None, motion=None, osd=None, compose=None, wall=None):
     """SSD.track_frames (see there)."""
     from .track import ByteTracker, with_analytics
     from .osd import check_overlay, painted
+    from .compose import check_composition, composed
     if model.training:
         raise ValueError("track_frames: the model must be in eval mode")
     if not isinstance(tracker, ByteTracker):
@@ -211,16 +212,18 @@ def track_frames(model, batch: FrameBatch, tracker, analytics=None, motion=None,
         from .motion import check_motion, compensated
         check_motion(motion, tracker, batch, "track_frames")
     check_overlay(osd, tracker, "track_frames")
+    check_composition(compose, wall, batch, "track_frames")
     boxes, scores, labels, counts = forward_frames(model, batch)
     if motion is not None:
         compensated(motion, tracker, batch, boxes, scores, counts)
-    return painted(with_analytics(tracker.update(boxes, scores, labels, counts), analytics), osd, batch, analytics)
+    return composed(painted(with_analytics(tracker.update(boxes, scores, labels, counts), analytics), osd, batch, analytics), compose, batch, wall)
 
 
-def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder, analytics=None, motion=None, osd=None):
+def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder, analytics=None, motion=None, osd=None, compose=None, wall=None):
     """SSD.track_frames_appearance (see there)."""
     from .crops import ObjectCropper
     from .osd import check_overlay, painted
+    from .compose import check_composition, composed
     from .track import AppearanceTracker, with_analytics
     if model.training:
         raise ValueError("track_frames_appearance: the model must be in eval mode")
@@ -237,6 +240,7 @@ def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder
         from .motion import check_motion, compensated
         check_motion(motion, tracker, batch, "track_frames_appearance")
     check_overlay(osd, tracker, "track_frames_appearance")
+    check_composition(compose, wall, batch, "track_frames_appearance")
     boxes, scores, labels, counts = forward_frames(model, batch)
     if motion is not None:
         compensated(motion, tracker, batch, boxes, scores, counts)
@@ -246,7 +250,8 @@ def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder
     if not isinstance(emb, Tensor) or tuple(emb.shape) != (cropper.capacity, tracker.dim):
         raise ValueError("track_frames_appearance: the embedder must return [{}, {}], got {}".format(
             cropper.capacity, tracker.dim, tuple(emb.shape) if isinstance(emb, Tensor) else type(emb)))
-    return painted(with_analytics(tracker.update(boxes, scores, labels, counts, emb.contiguous(), index), analytics), osd, batch, analytics)
+    return composed(painted(with_analytics(tracker.update(boxes, scores, labels, counts, emb.contiguous(), index), analytics), osd, batch, analytics),
+                    compose, batch, wall)
 
 
 # ---------------------------------------------------------------------------------------------------------------- regions

@@ -1001,6 +1001,65 @@ DN_API int dn_osd_paint(const dn_frame* frames_dev, int n, int format, const flo
                         const uint8_t* names_dev, const dn_osd_color* palette_dev, const uint8_t* font_dev, const dn_zone_config* zone_config_dev,
                         const dn_osd_params* params, void* workspace_dev, size_t workspace_bytes, int32_t* stats_dev, void* stream);
 
+/* Surface composition on the device (csrc/compose.hip): rectangles of the surfaces of one dn_frame table are scaled, converted and
+ * written into rectangles of the surfaces of another -- 64 painted streams into one wall surface, a preview per camera, NV12 to RGB for a snapshot,
+ * pitched BGR to NV12 for an encoder. demonet_amd/compose.py (Compositor) is the caller; tests/compose_ref.py restates these sentences in numpy.
+ * Tables. src_frames_dev / dst_frames_dev: dn_frame tables (formats and colour codes: dn_forward_frames'), every record of a table in the table's
+ * format; the destination surfaces are written. table_dev: a 16-byte dn_compose_header followed by `capacity` 48-byte dn_compose_item records, in
+ * DEVICE memory, read WHEN THE KERNEL RUNS: the call's arguments are addresses and the capacity only, so a captured graph follows new surfaces, new
+ * items and a new item count without a recapture. Item i copies the rectangle (sx0, sy0, sw, sh) of frame `src` of the source table to the rectangle
+ * (dx0, dy0, dw, dh) of frame `dst` of the destination table. tile0 is the item's first tile in the call's work list: tile0[0] = 0, tile0[i + 1] =
+ * tile0[i] + ceil(dw_i / 32) ceil(dh_i / 32), and header.n_tiles is the total; the caller computes them when it writes the table.
+ * Resampling is an exact area (box) filter per plane sample, in integers. Along x, for destination column j of dw over a source extent of sw, the weight
+ * of source column s is the length of [j sw, (j + 1) sw) intersected with [s dw, (s + 1) dw); the weights of a column sum to sw. Along y likewise with
+ * sh, dh. out = (sum over y, x of wy wx p + D / 2) / D with D = sw sh, integer division: the mean rounded half up. sw sh <= 2^24, so the unsigned
+ * 32-bit sum is exact. A 1:1 item is a byte copy; an upscale is nearest with blended seams.
+ * Plane-wise path: source and destination both NV12 / I420 (in any combination) AND src_color == dst_color. The Y plane is resampled from the source
+ * rectangle to the destination rectangle; U and V with the same filter from the chroma rectangle (sx0 / 2, sy0 / 2, ceil(sw / 2), ceil(sh / 2)) to
+ * (dx0 / 2, dy0 / 2, ceil(dw / 2), ceil(dh / 2)). No colour arithmetic; 1.5 bytes per source pixel are read.
+ * RGB path: every other pair (RGB / BGR <-> RGB / BGR, YUV -> RGB, RGB -> YUV, YUV -> YUV across matrix or range). Each source pixel becomes RGB8 by
+ * dn_forward_frames' integer formulas with src_color, its chroma sample (x >> 1, y >> 1) in FRAME coordinates; R, G and B are area-resampled per
+ * channel to one RGB8 per destination pixel. An RGB24 / BGR24 destination stores that RGB8. A YUV destination computes Y per pixel from its RGB8, and
+ * U, V per chroma sample from the per-channel mean, rounded half up ((sum + n / 2) / n), of the destination RGB8 pixels that lie in both its 2 x 2
+ * block and the rectangle (n = 1, 2 or 4). Y = clamp(((yr R + yg G + yb B + 2^13) >> 14) + yo), U = clamp(((ur R + ug G + ub B + 2^13) >> 14) + 128),
+ * V likewise (>> arithmetic, clamp to 0 .. 255), every coefficient round(c 2^14) of the BT.601 / BT.709 forward matrix of dst_color in limited
+ * (219/255, 224/255, yo = 16) or full range: dn_osd_paint's colour formula.
+ * One byte, one owner. For a YUV source sx0 and sy0 are even, for a YUV destination dx0 and dy0; rectangles lie wholly inside their frames; the
+ * destination rectangles of one destination surface do not overlap, their chroma footprints (dx0 / 2, dy0 / 2, ceil(dw / 2), ceil(dh / 2)) neither.
+ * Hence the result does not depend on the order of the work and is the same on every run. The bytes of a pitch gap and every payload byte of a
+ * destination no item covers keep every bit. Source and destination surfaces must not share memory.
+ * TRUST BOUNDARY: THE LIBRARY CANNOT INSPECT A DEVICE TABLE AND TRUSTS ALL THREE, THE ITEM TABLE EXACTLY LIKE dn_region: 0 <= n_items <= capacity,
+ * every index inside its frame table, every rectangle inside its frame with sides 1 .. 32768, sw sh <= 2^24, the parity and overlap rules above,
+ * tile0 and n_tiles (< 2^31) as defined, reserved words 0; a wrong record is an out-of-bounds device read or WRITE. Validate on the host before the
+ * records go up (Python: compose.Compositor.set, which also remembers both tables' sizes and refuses a call after they changed).
+ * One launch of persistent workgroups, asynchronous on `stream`, no host wait, no atomics; can be captured. DN_E_INVALID for a null table, frame tables
+ * not 8-byte or an item table not 16-byte aligned, capacity < 1, an unknown format or colour code; DN_E_UNSUPPORTED for capacity > 65536. Every error
+ * is raised before anything is enqueued.
+ * dn_surface_fill writes the PAYLOAD of the n whole surfaces of a table, not the gaps, with one colour: c0, c1, c2 are bytes (0 .. 255) in the
+ * surfaces' own space in logical order, (Y, U, V) or (R, G, B) as for dn_osd_paint; the caller converts. One launch, asynchronous, can be captured.
+ * DN_E_INVALID for a null or misaligned table, n < 1, an unknown format, a byte outside 0 .. 255; DN_E_UNSUPPORTED for n > 65535. */
+typedef struct dn_compose_item {     /* 48 bytes, DEVICE memory */
+    int32_t src;                     /* index into the source dn_frame table */
+    int32_t sx0, sy0, sw, sh;        /* the source rectangle, in that frame's pixels */
+    int32_t dst;                     /* index into the destination dn_frame table */
+    int32_t dx0, dy0, dw, dh;        /* the destination rectangle */
+    int32_t tile0;                   /* the item's first 32 x 32 tile in the work list (see above) */
+    int32_t reserved;                /* 0 */
+} dn_compose_item;
+typedef struct dn_compose_header {   /* 16 bytes, DEVICE memory, directly in front of the items */
+    int32_t n_items;                 /* 0 .. capacity */
+    int32_t n_tiles;                 /* the sum of the items' tiles */
+    int32_t reserved[2];             /* 0 */
+} dn_compose_header;
+#ifdef __cplusplus
+static_assert(sizeof(dn_compose_item) == 48 && sizeof(dn_compose_header) == 16, "dn_compose_item is 48 bytes, dn_compose_header 16");
+#else
+_Static_assert(sizeof(dn_compose_item) == 48 && sizeof(dn_compose_header) == 16, "dn_compose_item is 48 bytes, dn_compose_header 16");
+#endif
+DN_API int dn_compose(const dn_frame* src_frames_dev, int src_format, int src_color, const dn_frame* dst_frames_dev, int dst_format, int dst_color,
+                      const dn_compose_header* table_dev, int capacity, void* stream);
+DN_API int dn_surface_fill(const dn_frame* frames_dev, int n, int format, int c0, int c1, int c2, void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
