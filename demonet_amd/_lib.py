@@ -18,6 +18,8 @@ DN_SGD_CHUNK = 2048
 DN_SGD_MAX_GATE = 8
 DN_ZONE = dict(cross=1, enter=2, exit=3, vanish=4)
 DN_OSD_LABEL, DN_OSD_SCORE, DN_OSD_HIDE = 1, 2, 4
+DN_WARP_CELL = 8
+DN_WARP_BORDER = dict(constant=0, replicate=1)
 
 
 class TensorDesc(C.Structure):
@@ -100,6 +102,15 @@ class ComposeItem(C.Structure):
 
 class ComposeHeader(C.Structure):
     _fields_ = [("n_items", C.c_int32), ("n_tiles", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class WarpItem(C.Structure):
+    _fields_ = [("src", C.c_int32), ("dst", C.c_int32), ("dx0", C.c_int32), ("dy0", C.c_int32), ("dw", C.c_int32), ("dh", C.c_int32),
+                ("mesh0", C.c_int32), ("mesh_w", C.c_int32), ("flags", C.c_int32), ("border", C.c_int32), ("tile0", C.c_int32), ("reserved", C.c_int32)]
+
+
+class WarpHeader(C.Structure):
+    _fields_ = [("n_items", C.c_int32), ("n_tiles", C.c_int32), ("n_points", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ModelDesc(C.Structure):
@@ -206,6 +217,7 @@ _SIGNATURES = {
                      + [C.POINTER(OsdParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "dn_compose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dn_surface_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dn_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 # include/demonet_hip_debug.h: test support beside the boundary (not part of EXPORTS, which mirrors demonet_hip.h)

@@ -196,11 +196,12 @@ def forward_frames(model, batch: FrameBatch, packed=None):
     return b["outs"]
 
 
-def track_frames(model, batch: FrameBatch, tracker, analytics=None, motion=None, osd=None, compose=None, wall=None):
+def track_frames(model, batch: FrameBatch, tracker, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None, source=None):
     """SSD.track_frames (see there)."""
     from .track import ByteTracker, with_analytics
     from .osd import check_overlay, painted
     from .compose import check_composition, composed
+    from .warp import check_warping, warped
     if model.training:
         raise ValueError("track_frames: the model must be in eval mode")
     if not isinstance(tracker, ByteTracker):
@@ -213,15 +214,19 @@ def track_frames(model, batch: FrameBatch, tracker, analytics=None, motion=None,
         check_motion(motion, tracker, batch, "track_frames")
     check_overlay(osd, tracker, "track_frames")
     check_composition(compose, wall, batch, "track_frames")
+    check_warping(warp, source, batch, "track_frames")
+    warped(warp, source, batch)
     boxes, scores, labels, counts = forward_frames(model, batch)
     if motion is not None:
         compensated(motion, tracker, batch, boxes, scores, counts)
     return composed(painted(with_analytics(tracker.update(boxes, scores, labels, counts), analytics), osd, batch, analytics), compose, batch, wall)
 
 
-def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder, analytics=None, motion=None, osd=None, compose=None, wall=None):
+def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None,
+                            source=None):
     """SSD.track_frames_appearance (see there)."""
     from .crops import ObjectCropper
+    from .warp import check_warping, warped
     from .osd import check_overlay, painted
     from .compose import check_composition, composed
     from .track import AppearanceTracker, with_analytics
@@ -241,6 +246,8 @@ def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder
         check_motion(motion, tracker, batch, "track_frames_appearance")
     check_overlay(osd, tracker, "track_frames_appearance")
     check_composition(compose, wall, batch, "track_frames_appearance")
+    check_warping(warp, source, batch, "track_frames_appearance")
+    warped(warp, source, batch)
     boxes, scores, labels, counts = forward_frames(model, batch)
     if motion is not None:
         compensated(motion, tracker, batch, boxes, scores, counts)

@@ -323,8 +323,9 @@ def detect_sliced_frames(model, batch, tile=None, overlap: float = 0.25, full_im
     return [{"boxes": boxes[g, :c], "scores": scores[g, :c], "labels": labels[g, :c]} for g, c in enumerate(cnt)]
 
 
-def track_sliced_frames(model, batch, tracker, slicer: FrameSlicer, analytics=None, motion=None, osd=None, compose=None, wall=None):
+def track_sliced_frames(model, batch, tracker, slicer: FrameSlicer, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None, source=None):
     """SSD.track_sliced_frames (see there)."""
+    from .warp import check_warping, warped
     from .track import ByteTracker, MAX_D as TRACK_MAX_D, with_analytics
     from .osd import check_overlay, painted
     from .compose import check_composition, composed
@@ -339,10 +340,13 @@ def track_sliced_frames(model, batch, tracker, slicer: FrameSlicer, analytics=No
         check_analytics(analytics, tracker, "track_sliced_frames")
     check_overlay(osd, tracker, "track_sliced_frames")
     check_composition(compose, wall, batch, "track_sliced_frames")
+    check_warping(warp, source, batch, "track_sliced_frames")
     if motion is None:
+        warped(warp, source, batch)
         return composed(painted(with_analytics(tracker.update(*slicer(batch)), analytics), osd, batch, analytics), compose, batch, wall)
     from .motion import check_motion, compensated
     check_motion(motion, tracker, batch, "track_sliced_frames")
+    warped(warp, source, batch)
     boxes, scores, labels, counts = slicer(batch)
     compensated(motion, tracker, batch, boxes, scores, counts)
     return composed(painted(with_analytics(tracker.update(boxes, scores, labels, counts), analytics), osd, batch, analytics), compose, batch, wall)

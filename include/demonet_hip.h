@@ -1060,6 +1060,74 @@ DN_API int dn_compose(const dn_frame* src_frames_dev, int src_format, int src_co
                       const dn_compose_header* table_dev, int capacity, void* stream);
 DN_API int dn_surface_fill(const dn_frame* frames_dev, int n, int format, int c0, int c1, int c2, void* stream);
 
+/* Surface dewarping on the device (csrc/warp.hip): rectangles of the surfaces of one dn_frame table are filled from the surfaces of
+ * another through a coordinate mesh, with a bilinear filter -- virtual PTZ views and panoramas of a fisheye, lens undistortion, homographies, quarter
+ * turns, mirrors, bilinear scaling. demonet_amd/warp.py (Warper, and the host-side mesh builders) is the caller; tests/warp_ref.py restates these
+ * sentences in numpy integers, and the device matches them bit for bit. Both tables have the SAME format (`format`: dn_forward_frames' codes) and the
+ * same colour space: the remap works plane by plane on the stored bytes, colour conversion is dn_compose's job.
+ * Tables. table_dev: a 16-byte dn_warp_header followed by `capacity` 48-byte dn_warp_item records, in DEVICE memory, read WHEN THE KERNEL RUNS, like
+ * the frame tables and the meshes: a captured graph follows new surfaces, new items, new meshes and a new item count. Item i fills the rectangle
+ * (dx0, dy0, dw, dh) of frame `dst` of the destination table from frame `src` of the source table. tile0 and header.n_tiles are dn_compose's:
+ * tile0[0] = 0, tile0[i + 1] = tile0[i] + ceil(dw_i / 32) ceil(dh_i / 32).
+ * Mesh. mesh_dev: int32 [M][2], every mesh of the call; header.n_points = M. The mesh of an item is the mw x mh points, row-major, from point mesh0
+ * on, mw = mesh_w = ceil(dw / DN_WARP_CELL) + 1, mh = ceil(dh / DN_WARP_CELL) + 1; items may share a mesh. Point (cx, cy) = (X, Y) is the source
+ * position of rectangle pixel (8 cx, 8 cy) in units of 1/64 source pixel; coordinates are pixel indices, an integer is a pixel centre;
+ * |X|, |Y| <= 2^21 - 1. The points past the rectangle's end are part of the mesh.
+ * Luma and packed RGB / BGR pixel (x, y) of the rectangle: cx = x >> 3, i = x & 7, cy = y >> 3, j = y & 7; A, B, C, D the points (cx, cy),
+ * (cx + 1, cy), (cx, cy + 1), (cx + 1, cy + 1); per coordinate
+ *     P = (8 - j) ((8 - i) A + i B) + j ((8 - i) C + i D)          in 1/4096 pixel, |P| < 2^27
+ *     q = (P + 64) >> 7                                            in 1/32 pixel; >> of a signed value: arithmetic (floor)
+ *     x0 = qx >> 5, fx = qx & 31, y0 = qy >> 5, fy = qy & 31; taps p00 = (x0, y0), p01 = (x0 + 1, y0), p10 = (x0, y0 + 1), p11 = (x0 + 1, y0 + 1)
+ *     out = ((32 - fx) (32 - fy) p00 + fx (32 - fy) p01 + (32 - fx) fy p10 + fx fy p11 + 512) >> 10        per byte channel
+ * Chroma sample (cxs, cys) of a 4:2:0 rectangle; the chroma rectangle is (dx0 / 2, dy0 / 2, ceil(dw / 2), ceil(dh / 2)) as for dn_compose, the siting
+ * centred: the sample sits at luma position (2 cxs + 0.5, 2 cys + 0.5). With x = 2 cxs, y = 2 cys: cx = x >> 3, i2 = 2 (x & 7) + 1, cy = y >> 3,
+ * j2 = 2 (y & 7) + 1,
+ *     P2 = (16 - j2) ((16 - i2) A + i2 B) + j2 ((16 - i2) C + i2 D)    in 1/16384 luma pixel, |P2| < 2^29
+ *     qc = ((P2 + 512) >> 10) - 8                                      in 1/32 chroma sample
+ * taps and blend as above on the chroma plane(s) of ceil(W / 2) x ceil(H / 2) samples; NV12 reads U and V at the same taps.
+ * Hence an identity mesh is a byte copy of every plane, and quarter turns and mirrors are exact permutations of every plane for even-sized 4:2:0
+ * frames and for RGB of any size. There is no anti-aliasing filter: minify strongly with dn_compose's area filter behind the warp.
+ * Border. Every tap is tested on its own against its plane, 0 <= x < W, 0 <= y < H. flags = DN_WARP_BORDER_CONSTANT: a tap outside takes the item's
+ * border byte of that plane or channel, border = c0 | c1 << 8 | c2 << 16 with (c0, c1, c2) = (Y, U, V) for NV12 / I420 and the three bytes of a
+ * packed pixel IN MEMORY ORDER for RGB24 / BGR24 (one kernel serves both); DN_WARP_BORDER_REPLICATE: the tap's coordinates are clamped to the plane.
+ * Because of these tests NO MESH VALUE CAN MAKE THE KERNEL READ OUTSIDE A SURFACE.
+ * One byte, one owner. Destination rectangles lie inside their frames, sides 1 .. 32768; dx0 and dy0 are even on NV12 / I420; the rectangles of one
+ * destination surface do not overlap, their chroma footprints neither; source and destination surfaces share no memory. Hence the result does not
+ * depend on the order of the work, and the bytes of a pitch gap and every payload byte no item covers keep every bit.
+ * TRUST BOUNDARY: THE LIBRARY CANNOT INSPECT A DEVICE TABLE AND TRUSTS THE ITEM TABLE EXACTLY LIKE dn_region: 0 <= n_items <= capacity, every index
+ * inside its frame table, the rectangle rules above, mesh0 >= 0 and mesh0 + mw mh <= M with mesh_w = mw, tile0 and n_tiles (< 2^31) as defined,
+ * flags 0 or 1, reserved words 0; a wrong record is an out-of-bounds device read or WRITE. Validate on the host before the records go up (Python:
+ * warp.Warper.set, which also remembers both tables' sizes and refuses a call after they changed).
+ * One launch of persistent workgroups, asynchronous on `stream`, no host wait, no atomics, no workspace; can be captured. DN_E_INVALID for a null
+ * pointer, frame tables or a mesh not 8-byte or an item table not 16-byte aligned, capacity <= 0; DN_E_UNSUPPORTED for an unknown format or
+ * capacity > 65536. Every error is raised before anything is enqueued. */
+#define DN_WARP_CELL 8
+enum { DN_WARP_BORDER_CONSTANT = 0, DN_WARP_BORDER_REPLICATE = 1 };
+typedef struct dn_warp_item {        /* 48 bytes, DEVICE memory */
+    int32_t src;                     /* index into the source dn_frame table */
+    int32_t dst;                     /* index into the destination dn_frame table */
+    int32_t dx0, dy0, dw, dh;        /* the destination rectangle */
+    int32_t mesh0;                   /* the first point of the item's mesh in mesh_dev */
+    int32_t mesh_w;                  /* points per mesh row: ceil(dw / 8) + 1 */
+    int32_t flags;                   /* DN_WARP_BORDER_* */
+    int32_t border;                  /* c0 | c1 << 8 | c2 << 16 (see above) */
+    int32_t tile0;                   /* the item's first 32 x 32 tile in the work list */
+    int32_t reserved;                /* 0 */
+} dn_warp_item;
+typedef struct dn_warp_header {      /* 16 bytes, DEVICE memory, directly in front of the items */
+    int32_t n_items;                 /* 0 .. capacity */
+    int32_t n_tiles;                 /* the sum of the items' tiles */
+    int32_t n_points;                /* M, the points of mesh_dev */
+    int32_t reserved;                /* 0 */
+} dn_warp_header;
+#ifdef __cplusplus
+static_assert(sizeof(dn_warp_item) == 48 && sizeof(dn_warp_header) == 16, "dn_warp_item is 48 bytes, dn_warp_header 16");
+#else
+_Static_assert(sizeof(dn_warp_item) == 48 && sizeof(dn_warp_header) == 16, "dn_warp_item is 48 bytes, dn_warp_header 16");
+#endif
+DN_API int dn_warp(const dn_frame* src_frames_dev, const dn_frame* dst_frames_dev, int format, const void* table_dev, int capacity,
+                   const int32_t* mesh_dev, void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
