@@ -22,6 +22,10 @@ DN_WARP_CELL = 8
 DN_WARP_BORDER = dict(constant=0, replicate=1)
 
 
+DN_JPEG_MAX_ITEMS = 8192
+DN_JPEG_HEADER_BYTES = 613
+
+
 class TensorDesc(C.Structure):
     _fields_ = [("c", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("kind", C.c_int32)]
 
@@ -102,6 +106,15 @@ class ComposeItem(C.Structure):
 
 class ComposeHeader(C.Structure):
     _fields_ = [("n_items", C.c_int32), ("n_tiles", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class JpegItem(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("quality", C.c_int32),
+                ("seg0", C.c_int32), ("reserved", C.c_int32)]
+
+
+class JpegHeader(C.Structure):
+    _fields_ = [("n_items", C.c_int32), ("n_segments", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class WarpItem(C.Structure):
@@ -218,6 +231,9 @@ _SIGNATURES = {
     "dn_compose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dn_surface_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dn_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "dn_jpeg_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "dn_jpeg_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dn_jpeg_items_from_index": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 # include/demonet_hip_debug.h: test support beside the boundary (not part of EXPORTS, which mirrors demonet_hip.h)

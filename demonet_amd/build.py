@@ -4,7 +4,7 @@
 
 One object per .hip file (postprocess.hip, sliced.hip, evalmatch.hip, cocomatch.hip, augment.hip, optim.hip, fuse.hip, track.hip, trackapp.hip, zones.hip, crops.hip, motion.hip, osd.hip, compose.hip and detset.hip with -ffp-contract=off: decode/IoU must round like the
 reference, the augmentation like its fp32 emulation, the SGD update like torch.optim.SGD, the box fusion, the tracker and its appearance step, the zone analytics, the object crops behind it, the camera-motion compensation and the on-screen display like their float32 restatements,
-and detset.hip, the ranking that merge and fusion share, is built like its two users),
+and detset.hip, the ranking that merge and fusion share, is built like its two users; jpeg.hip, the baseline JPEG encoder of DESIGN 4y, is integer code and takes no extra flag),
 linked into one C-ABI shared library. In-tree output so the .so travels with the repo snapshot to the GPU box.
 """
 import os
@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdemonet_hip.so")
-SOURCES = ["plan.hip", "pointwise.hip", "depthwise.hip", "dense.hip", "postprocess.hip", "expdw.hip", "expdw_direct.hip", "expdw_rows.hip", "expdw_whole.hip", "tail.hip", "convbig.hip", "pwdirect.hip", "loss.hip", "headfuse.hip", "headgrad.hip", "sliced.hip", "evalmatch.hip", "cocomatch.hip", "augment.hip", "optim.hip", "fuse.hip", "track.hip", "trackapp.hip", "detset.hip", "zones.hip", "crops.hip", "motion.hip", "osd.hip", "compose.hip", "warp.hip"]
+SOURCES = ["plan.hip", "pointwise.hip", "depthwise.hip", "dense.hip", "postprocess.hip", "expdw.hip", "expdw_direct.hip", "expdw_rows.hip", "expdw_whole.hip", "tail.hip", "convbig.hip", "pwdirect.hip", "loss.hip", "headfuse.hip", "headgrad.hip", "sliced.hip", "evalmatch.hip", "cocomatch.hip", "augment.hip", "optim.hip", "fuse.hip", "track.hip", "trackapp.hip", "detset.hip", "zones.hip", "crops.hip", "motion.hip", "osd.hip", "compose.hip", "warp.hip", "jpeg.hip"]
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs, not AGPRs -- the small-tile kernels otherwise spend a v_accvgpr_read per
 # accumulator value on the way to their epilogues (not for convbig.hip: its 256 x 256 tiles need the AGPR half of the file)
 VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]

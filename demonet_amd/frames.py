@@ -196,12 +196,13 @@ def forward_frames(model, batch: FrameBatch, packed=None):
     return b["outs"]
 
 
-def track_frames(model, batch: FrameBatch, tracker, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None, source=None):
+def track_frames(model, batch: FrameBatch, tracker, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None, source=None, jpeg=None):
     """SSD.track_frames (see there)."""
     from .track import ByteTracker, with_analytics
     from .osd import check_overlay, painted
     from .compose import check_composition, composed
     from .warp import check_warping, warped
+    from .jpeg import check_jpeg, encoded
     if model.training:
         raise ValueError("track_frames: the model must be in eval mode")
     if not isinstance(tracker, ByteTracker):
@@ -215,21 +216,24 @@ def track_frames(model, batch: FrameBatch, tracker, analytics=None, motion=None,
     check_overlay(osd, tracker, "track_frames")
     check_composition(compose, wall, batch, "track_frames")
     check_warping(warp, source, batch, "track_frames")
+    check_jpeg(jpeg, wall, batch, "track_frames")
     warped(warp, source, batch)
     boxes, scores, labels, counts = forward_frames(model, batch)
     if motion is not None:
         compensated(motion, tracker, batch, boxes, scores, counts)
-    return composed(painted(with_analytics(tracker.update(boxes, scores, labels, counts), analytics), osd, batch, analytics), compose, batch, wall)
+    return encoded(composed(painted(with_analytics(tracker.update(boxes, scores, labels, counts), analytics), osd, batch, analytics), compose, batch, wall),
+                   jpeg, wall, batch)
 
 
 def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None,
-                            source=None):
+                            source=None, jpeg=None):
     """SSD.track_frames_appearance (see there)."""
     from .crops import ObjectCropper
     from .warp import check_warping, warped
     from .osd import check_overlay, painted
     from .compose import check_composition, composed
     from .track import AppearanceTracker, with_analytics
+    from .jpeg import check_jpeg, encoded
     if model.training:
         raise ValueError("track_frames_appearance: the model must be in eval mode")
     if not isinstance(tracker, AppearanceTracker):
@@ -247,6 +251,7 @@ def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder
     check_overlay(osd, tracker, "track_frames_appearance")
     check_composition(compose, wall, batch, "track_frames_appearance")
     check_warping(warp, source, batch, "track_frames_appearance")
+    check_jpeg(jpeg, wall, batch, "track_frames_appearance")
     warped(warp, source, batch)
     boxes, scores, labels, counts = forward_frames(model, batch)
     if motion is not None:
@@ -257,8 +262,8 @@ def track_frames_appearance(model, batch: FrameBatch, tracker, cropper, embedder
     if not isinstance(emb, Tensor) or tuple(emb.shape) != (cropper.capacity, tracker.dim):
         raise ValueError("track_frames_appearance: the embedder must return [{}, {}], got {}".format(
             cropper.capacity, tracker.dim, tuple(emb.shape) if isinstance(emb, Tensor) else type(emb)))
-    return composed(painted(with_analytics(tracker.update(boxes, scores, labels, counts, emb.contiguous(), index), analytics), osd, batch, analytics),
-                    compose, batch, wall)
+    return encoded(composed(painted(with_analytics(tracker.update(boxes, scores, labels, counts, emb.contiguous(), index), analytics), osd, batch, analytics),
+                            compose, batch, wall), jpeg, wall, batch)
 
 
 # ---------------------------------------------------------------------------------------------------------------- regions

@@ -323,12 +323,14 @@ def detect_sliced_frames(model, batch, tile=None, overlap: float = 0.25, full_im
     return [{"boxes": boxes[g, :c], "scores": scores[g, :c], "labels": labels[g, :c]} for g, c in enumerate(cnt)]
 
 
-def track_sliced_frames(model, batch, tracker, slicer: FrameSlicer, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None, source=None):
+def track_sliced_frames(model, batch, tracker, slicer: FrameSlicer, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None, source=None,
+                        jpeg=None):
     """SSD.track_sliced_frames (see there)."""
     from .warp import check_warping, warped
     from .track import ByteTracker, MAX_D as TRACK_MAX_D, with_analytics
     from .osd import check_overlay, painted
     from .compose import check_composition, composed
+    from .jpeg import check_jpeg, encoded
     if not isinstance(tracker, ByteTracker):
         raise ValueError("track_sliced_frames: tracker must be a ByteTracker, got {}".format(type(tracker)))
     if not isinstance(slicer, FrameSlicer) or slicer.model is not model:
@@ -341,12 +343,15 @@ def track_sliced_frames(model, batch, tracker, slicer: FrameSlicer, analytics=No
     check_overlay(osd, tracker, "track_sliced_frames")
     check_composition(compose, wall, batch, "track_sliced_frames")
     check_warping(warp, source, batch, "track_sliced_frames")
+    check_jpeg(jpeg, wall, batch, "track_sliced_frames")
     if motion is None:
         warped(warp, source, batch)
-        return composed(painted(with_analytics(tracker.update(*slicer(batch)), analytics), osd, batch, analytics), compose, batch, wall)
+        return encoded(composed(painted(with_analytics(tracker.update(*slicer(batch)), analytics), osd, batch, analytics), compose, batch, wall),
+                       jpeg, wall, batch)
     from .motion import check_motion, compensated
     check_motion(motion, tracker, batch, "track_sliced_frames")
     warped(warp, source, batch)
     boxes, scores, labels, counts = slicer(batch)
     compensated(motion, tracker, batch, boxes, scores, counts)
-    return composed(painted(with_analytics(tracker.update(boxes, scores, labels, counts), analytics), osd, batch, analytics), compose, batch, wall)
+    return encoded(composed(painted(with_analytics(tracker.update(boxes, scores, labels, counts), analytics), osd, batch, analytics), compose, batch, wall),
+                   jpeg, wall, batch)

@@ -413,7 +413,7 @@ class SSD(_Tracked):
         from .frames import forward_frames
         return forward_frames(self, batch, packed)
 
-    def track_frames(self, batch, tracker, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None, source=None):
+    def track_frames(self, batch, tracker, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None, source=None, jpeg=None):
         """`track` on top of forward_frames: frame b of the FrameBatch is the current frame of stream b. Returns what ByteTracker.update returns;
         analytics as in `track`. motion: a motion.MotionCompensator for a moving camera: forward -> motion.estimate(batch, that
         frame's detections) -> tracker.compensate -> update; None (the default): exactly the calls above. osd: an osd.Overlay: the
@@ -424,20 +424,23 @@ class SSD(_Tracked):
         surfaces, compose(batch, wall); both or neither; None (the default): exactly the calls above. warp, source: a warp.Warper that was set()
         for (source, batch) and its source FrameBatch: as the step's FIRST act, in front of the forward, the batch's frames are filled
         from the source's surfaces -- views of a fisheye, an undistorted or a turned camera --, warp(source, batch); both or neither; None (the
-        default): exactly the calls above."""
+        default): exactly the calls above. jpeg: a jpeg.JpegEncoder that was set() for the wall when the step has one, for the batch
+        otherwise: behind the paint and the composition its items are coded into its arena, jpeg.encode(wall or batch); None (the default):
+        exactly the calls above."""
         from .frames import track_frames
-        return track_frames(self, batch, tracker, analytics, motion, osd, compose, wall, warp, source)
+        return track_frames(self, batch, tracker, analytics, motion, osd, compose, wall, warp, source, jpeg)
 
     def track_frames_appearance(self, batch, tracker, cropper, embedder, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None,
-                                source=None):
+                                source=None, jpeg=None):
         """`track_frames` with appearance, nothing leaving the device: forward_frames; cropper(batch, boxes, counts, select) with
         select = scores >= the tracker's track_thresh, built on the device; embedder(patches), any callable that returns a [capacity, dim] fp16
         or fp32 device tensor (the re-identification model: not part of this package); tracker.update(..., embeddings, cropper.index) for a
         track.AppearanceTracker; then the analytics as in `track`. Returns what ByteTracker.update returns. motion: as in `track_frames`
         (estimate and compensate run behind the forward, in front of the crops). osd: as in `track_frames` (the paint follows the crops). compose, wall:
-        as in `track_frames` (the composition follows the paint). warp, source: as in `track_frames` (the warp precedes the forward)."""
+        as in `track_frames` (the composition follows the paint). warp, source: as in `track_frames` (the warp precedes the forward). jpeg: as in
+        `track_frames` (the encoder runs last)."""
         from .frames import track_frames_appearance
-        return track_frames_appearance(self, batch, tracker, cropper, embedder, analytics, motion, osd, compose, wall, warp, source)
+        return track_frames_appearance(self, batch, tracker, cropper, embedder, analytics, motion, osd, compose, wall, warp, source, jpeg)
 
     def forward_regions(self, batch, table, packed: Optional[Tensor] = None):
         """The forward on REGIONS of video surfaces (demonet_amd/frames.py): table is a frames.RegionTable of n (frame, x0, y0, w, h[,
@@ -464,13 +467,14 @@ class SSD(_Tracked):
         from .fusion import detect_tta_frames
         return detect_tta_frames(self, batch, fuse, thresh, skip_thresh)
 
-    def track_sliced_frames(self, batch, tracker, slicer, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None, source=None):
+    def track_sliced_frames(self, batch, tracker, slicer, analytics=None, motion=None, osd=None, compose=None, wall=None, warp=None, source=None,
+                            jpeg=None):
         """Video -> tiles -> merge -> ByteTrack without a host wait per frame step: tracker.update(*slicer(batch)) for a sliced.FrameSlicer of
         this model (frame g of the batch is the current frame of stream g). Returns what ByteTracker.update returns; analytics as in `track`.
         ValueError when detections_per_img exceeds the tracker's 512 rows. motion: as in `track_frames`, with the merged detections. osd, compose and
-        wall: as in `track_frames`; warp and source too (the warp precedes the tiles)."""
+        wall: as in `track_frames`; warp and source too (the warp precedes the tiles); jpeg too (the encoder runs last)."""
         from .sliced import track_sliced_frames
-        return track_sliced_frames(self, batch, tracker, slicer, analytics, motion, osd, compose, wall, warp, source)
+        return track_sliced_frames(self, batch, tracker, slicer, analytics, motion, osd, compose, wall, warp, source, jpeg)
 
     def paint_frames(self, batch, overlay, boxes, scores, labels, counts, ids=None, zones=None):
         """On-screen display (demonet_amd/osd.py): overlay.paint(batch, boxes, scores, labels, counts, ids, zones) for an osd.Overlay on

@@ -1128,6 +1128,87 @@ _Static_assert(sizeof(dn_warp_item) == 48 && sizeof(dn_warp_header) == 16, "dn_w
 DN_API int dn_warp(const dn_frame* src_frames_dev, const dn_frame* dst_frames_dev, int format, const void* table_dev, int capacity,
                    const int32_t* mesh_dev, void* stream);
 
+/* Baseline JPEG encoding of surface rectangles on the device (csrc/jpeg.hip): rectangles of the surfaces of a dn_frame table become
+ * complete .jpg files (ITU-T T.81 baseline sequential, JFIF 1.01) in one device byte arena -- the snapshot of an event, the thumbnail of a tracked
+ * object, a redacted evidence frame. demonet_amd/jpeg.py (JpegEncoder) is the caller; tests/jpeg_ref.py restates these sentences in numpy and
+ * integers, with a decoder of its own, and the device matches it byte for byte.
+ * Tables. frames_dev: a dn_frame table (format, color: dn_forward_frames' codes). table_dev: a 16-byte dn_jpeg_header followed by `capacity_items`
+ * 32-byte dn_jpeg_item records, in DEVICE memory, read WHEN THE KERNELS RUN: the call's arguments are addresses and capacities only, so a captured
+ * graph follows new surfaces, new items and a new item count without a recapture. Item i is the rectangle (x0, y0, width, height) of frame `frame`
+ * at quality 1 .. 100, or a slot without a file: frame = -1 an empty slot (status 1), -2 a refused rectangle (2), -3 no space in the work list (3),
+ * all three with width = height = 0; slots at or beyond n_items are empty. seg0 is the item's first MCU row in the call's work list: seg0[0] = 0,
+ * seg0[i + 1] = seg0[i] + ceil(height_i / 16) (a slot without a file has no rows), header.n_segments the total.
+ * Components. Three, YCbCr as JFIF defines it (BT.601, full range), 4:2:0: the MCU is 16 x 16, four Y blocks, then Cb, then Cr.
+ * Plane-wise path: format NV12 / I420 AND color == DN_COLOR_BT601 | DN_COLOR_FULL_RANGE. The component planes are the stored bytes: Y the rectangle,
+ * Cb and Cr the chroma rectangle (x0 / 2, y0 / 2, ceil(width / 2), ceil(height / 2)) -- dn_compose's plane-wise rule, no colour arithmetic.
+ * RGB path: every other table. Each pixel becomes RGB8 by dn_forward_frames' integer formulas (chroma sample (X >> 1, Y >> 1) in FRAME coordinates);
+ * Y per pixel, Cb and Cr per chroma sample from the rounded-half-up mean of the RGB8 pixels that lie in both its 2 x 2 block of the rectangle and
+ * the rectangle, by dn_compose's forward formula with the BT.601 full-range coefficients: the planes a 1:1 dn_compose item into an I420 BT.601
+ * full-range surface of width x height would hold. For NV12 / I420 x0 and y0 are even.
+ * Edge. Samples of a partial MCU beyond a component plane replicate that plane's last column and last row.
+ * Transform. Level shift by -128, then the 8 x 8 forward DCT in integers: the Loeffler-Ligtenberg-Moschytz form, rows then columns, constants
+ * round(c 2^13), the row pass scaled up by 2^2, descales rounded half up with an arithmetic shift; the output is 8 times the orthonormal DCT
+ * (tests/jpeg_ref.py, fdct, is the statement).
+ * Quantisation. The Annex K luminance and chrominance tables scaled by the IJG quality rule in integers: s = q < 50 ? 5000 / q : 200 - 2 q,
+ * Q = clamp((base s + 50) / 100, 1, 255); coefficient = sign(c) ((|c| + d / 2) / d) with d = 8 Q. The kernels derive the tables from `quality`.
+ * Entropy coding. Zigzag order, the four Annex K "typical" Huffman tables, written into every file; one DC predictor per component; ZRL and EOB as in
+ * T.81; bits MSB first, a 0x00 behind every 0xFF data byte. One MCU row is one restart interval: DRI = ceil(width / 16), RSTm with m = row mod 8
+ * behind every row but the last, the predictors reset at every row, the last byte of a row padded with 1-bits.
+ * File: SOI, APP0 (JFIF 1.01, density 1:1, no thumbnail), one DQT (both 8-bit tables), SOF0, one DHT (DC0, AC0, DC1, AC1), DRI, SOS, data, EOI;
+ * the segments in front of the data are 613 bytes.
+ * Results. results_dev: [capacity_items][4] int32 rows (offset, length, status, 0); totals_dev: [4] int32 (written, refused, bytes_used, 0) with
+ * refused the slots of status 2 or 3 and bytes_used the end of the last written file. Status 0 written, 1 empty slot, 2 rectangle refused, 3 no
+ * space. Placement is a pure prefix sum: offset_i is the sum of (length_j + 15) & ~15 over every encodable j < i whether or not j fitted; item i is
+ * written iff offset_i + length_i <= arena_bytes, otherwise status 3, length 0, and no byte of the arena is written on its behalf. The bytes of the
+ * alignment gaps and everything beyond bytes_used keep their contents. Two calls on equal inputs give equal bytes: no float, no order dependence.
+ * Three launches, asynchronous on `stream`, no host wait, can be captured: every MCU row is coded once for its exact stuffed length, one workgroup
+ * scans row and file lengths into offsets, results and totals, and every row is coded again at its final place (nothing is sized by a guessed
+ * compression ratio). workspace_dev: dn_jpeg_workspace_bytes(capacity_items, max_segments) bytes, 16-byte aligned, for a work list of at most max_segments
+ * MCU rows (4 bytes per row and per item); the kernels cut a table whose n_segments exceeds what workspace_bytes holds at that many rows, so that
+ * no table makes them write outside the workspace (the rows beyond are not coded: the caller's validation keeps this from happening).
+ * TRUST BOUNDARY: THE LIBRARY CANNOT INSPECT A DEVICE TABLE AND TRUSTS THE ITEM TABLE OF dn_jpeg_encode EXACTLY LIKE dn_compose's: 0 <= n_items <=
+ * capacity_items, every frame index inside the frame table, every rectangle inside its frame with sides 1 .. 32768, even origins on NV12 / I420,
+ * quality 1 .. 100, seg0 and n_segments as defined, reserved words 0; a wrong record is an out-of-bounds device read. Validate on the host before
+ * the records go up (Python: jpeg.JpegEncoder.set) -- or let dn_jpeg_items_from_index write the table.
+ * DN_E_INVALID for a null table, arena, result or workspace pointer, frame tables not 8-byte or an item table, results, totals or workspace not
+ * 16-byte aligned, capacity_items < 1, arena_bytes < 0, an unknown format or colour code, a workspace below
+ * dn_jpeg_workspace_bytes(capacity_items, 1); DN_E_UNSUPPORTED for capacity_items > 8192 (dn_jpeg_workspace_bytes then returns 0). Every error is raised before
+ * anything is enqueued.
+ * dn_jpeg_items_from_index writes such a table from an object cropper's index table (dn_crop_objects): index_dev = [index_rows][8] int32 rows
+ * (stream, row, x0, y0, width, height, 0, 0), stream -1 an unused slot; item s is index row s, header.n_items = index_rows, and table_dev holds at
+ * least index_rows item records behind its header. THE ROWS ARE NOT
+ * TRUSTED: a stream outside [0, n_frames), a side below 1 or above 32768 or a rectangle not wholly inside that frame's record gives status 2. For
+ * NV12 / I420 an odd x0 or y0 moves down to the even pixel and that side grows by one. select_dev (may be null): [index_rows] bytes, 0 deselects the
+ * slot; unused and deselected slots give status 1. A slot whose rows would push the segment total past max_segments gives status 3 (the total
+ * counts every valid slot in front of it, so every valid slot behind it has status 3 too). seg0 comes from a block scan in slot order. One small
+ * launch, can be captured. DN_E_INVALID for a null pointer (select_dev excepted), a frame table not 8-byte or an index or item table not 16-byte
+ * aligned, n_frames < 1, index_rows < 1, max_segments < 1, quality outside 1 .. 100, an unknown format; DN_E_UNSUPPORTED for index_rows > 8192. */
+#define DN_JPEG_MAX_ITEMS 8192
+#define DN_JPEG_HEADER_BYTES 613
+typedef struct dn_jpeg_item {        /* 32 bytes, DEVICE memory */
+    int32_t frame;                   /* index into the dn_frame table; -1, -2, -3: a slot without a file (status 1, 2, 3) */
+    int32_t x0, y0, width, height;   /* the rectangle, in that frame's pixels */
+    int32_t quality;                 /* 1 .. 100 */
+    int32_t seg0;                    /* the item's first MCU row in the work list (see above) */
+    int32_t reserved;                /* 0 */
+} dn_jpeg_item;
+typedef struct dn_jpeg_header {      /* 16 bytes, DEVICE memory, directly in front of the items */
+    int32_t n_items;                 /* 0 .. capacity_items */
+    int32_t n_segments;              /* the sum of the items' MCU rows, < 2^31 */
+    int32_t reserved[2];             /* 0 */
+} dn_jpeg_header;
+#ifdef __cplusplus
+static_assert(sizeof(dn_jpeg_item) == 32 && sizeof(dn_jpeg_header) == 16, "dn_jpeg_item is 32 bytes, dn_jpeg_header 16");
+#else
+_Static_assert(sizeof(dn_jpeg_item) == 32 && sizeof(dn_jpeg_header) == 16, "dn_jpeg_item is 32 bytes, dn_jpeg_header 16");
+#endif
+DN_API size_t dn_jpeg_workspace_bytes(int capacity_items, int max_segments);
+DN_API int dn_jpeg_encode(const dn_frame* frames_dev, int format, int color, const dn_jpeg_header* table_dev, int capacity_items,
+                          uint8_t* arena_dev, int arena_bytes, int32_t* results_dev, int32_t* totals_dev, void* workspace_dev, size_t workspace_bytes,
+                          void* stream);
+DN_API int dn_jpeg_items_from_index(const dn_frame* frames_dev, int n_frames, int format, const int32_t* index_dev, int index_rows,
+                                    const uint8_t* select_dev, int quality, int max_segments, dn_jpeg_header* table_dev, void* stream);
+
 DN_API const char* dn_last_error(void);
 DN_API int dn_abi_version(void);
 
